@@ -26,6 +26,15 @@ controller's one redrawn buffer would).  ``c3`` remains the headline line.
 scaling (K fixed, split over the ranks), 28 B of noise per state-step, the
 config-5 start pose on xydq_circle.txt and gravity-holding nominal torques.
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.
+``--full`` adds every other leg after the timed steps: the drop-in's
+control-step latencies, the CPU baselines and, at N > 1, the per-step cost of
+each exchange.  ``--dump-outputs DIR`` writes what the last timed step left for
+its caller (the shifted nominal controls and the weighted noise sum, fp64) as
+``DIR/<name>.npy``.  After the clock settle (a time, not a count) the start
+nominal is staged again and the loop converged over a fixed number of untimed
+steps, so equal arguments give equal inputs to every timed step from run to run.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -101,7 +110,7 @@ def valu_roofline(tj, kern_ms):
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=1000)
+    p.add_argument("--steps", type=int, default=1000, help="timed steps")
     p.add_argument("--warmup", type=int, default=100)
     p.add_argument("--settle-ms", type=float, default=200.0,
                    help="untimed steps for this long before the W warmup steps: the GPU clock takes ~0.1 s of "
@@ -115,7 +124,14 @@ def parse():
     p.add_argument("--lps", type=int, default=0, help="lanes per sample (0 = auto; c5: 1 or 4)")
     p.add_argument("--precision", choices=("f32", "f64"), default="f32",
                    help="c5: rollout arithmetic of the chain (f64: for spread weights, DESIGN §3b)")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs beside the headline figure: the drop-in's "
+                        "control-step latencies, the CPU baselines (--cpu-seconds) and, at N > 1, the per-step cost "
+                        "of each exchange")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step left for its caller as DIR/<name>.npy (fp64): u_nominal "
+                        "(T, du), the shifted nominal controls, and w_eps (T, du), the weighted noise sum")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline budget (0 = skip)")
     p.add_argument("--traffic-json", default=None,
                    help="measured HBM bytes per launch (default profiles/traffic.json, c2/c5: profiles/traffic_<workload>.json)")
     p.add_argument("--launch", choices=("eager", "graph"), default="eager",
@@ -527,7 +543,7 @@ def main():
     # and replays it.
     use_graph = world == 1 and args.launch == "graph" and args.nbuf % 2 == 0 and not c5
     chunk = args.nbuf if use_graph else 1
-    steps = (args.steps + chunk - 1) // chunk * chunk
+    steps = args.steps   # graph replay: whole chunks, then the remainder as single launches
 
     xmode = "none" if world == 1 else "rccl"
     xreport = {}   # the step-1 self-check: which exchange, and why a fallback happened (distributed.py)
@@ -544,6 +560,7 @@ def main():
     # C5_RESET steps the start nominal is staged again (a 27 KB host-to-device copy, inside the timed region),
     # so the timed steps stay in the regime of a controller near its path.  The 2-DoF loop is stationary.
     C5_RESET = 32
+    CONVERGE_STEPS = 4000   # ~0.1 s at c3; the 200 ms settle phase alone ran ~7000
 
     def step(i, ev_pair=None):
         if c5 and i % C5_RESET == 0:
@@ -576,6 +593,13 @@ def main():
                 eng.rollout(noise[i % args.nbuf], partial_out=partial)
             i += 1
         torch.cuda.synchronize()
+    # the settle phase runs for a time, not a count, and every step moves the nominal: stage the start nominal
+    # again and converge the loop over a fixed number of untimed steps (the timed regime is the converged loop,
+    # its samples near the window; the chain loop is re-staged every C5_RESET steps anyway), so the W + N steps
+    # from here see the same inputs in every run (--dump-outputs compares builds)
+    eng.set_step_inputs(x0, window, u)
+    for i in range(0 if c5 else CONVERGE_STEPS):
+        step(i)
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
@@ -607,6 +631,8 @@ def main():
                 graph.replay()
             else:
                 step(c)
+        for c in range(nev * chunk, steps):
+            step(c)
         whole[1].record(stream)
     else:
         for c in range(nev):
@@ -636,11 +662,15 @@ def main():
         one = torch.ones(1, dtype=torch.float64, device=dev)
         dist.all_reduce(one, op=dist.ReduceOp.SUM)      # every rank took part in the timed region
         ranks_seen = int(one.item())
-    args.steps = steps
     eng.synchronize()   # raises if an in-launch hand-off timed out anywhere in the run (results invalid)
     u_final = eng.nominal()
     assert np.all(np.isfinite(u_final)), "non-finite nominal control"
-    xcosts = exchange_costs(eng, noise, partial, gathered, world, xmode, args) if world > 1 and not c5 else None
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "u_nominal.npy"), np.asarray(u_final, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "w_eps.npy"), np.asarray(eng.weighted_noise(), dtype=np.float64))
+    xcosts = (exchange_costs(eng, noise, partial, gathered, world, xmode, args)
+              if args.full and world > 1 and not c5 else None)
 
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
@@ -670,7 +700,7 @@ def main():
             "warmup": args.warmup, "settle_ms": args.settle_ms,
             "ms_per_step": ms_per_step,
             "rollouts_per_s": K_total * args.steps / elapsed,
-            "control_step_latency_ms": None,   # filled below (N = 1, c3): the drop-in's calc_control_input
+            "control_step_latency_ms": None,   # filled below (--full, N = 1, c3): the drop-in's calc_control_input
             "device_step_ms": ms_per_step,
             "kernel_ms": kern_ms,
             "higher_is_better": True,
@@ -699,7 +729,7 @@ def main():
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic},
             "valu_roofline": valu,
         }
-        if world == 1 and not c5:
+        if args.full and world == 1 and not c5:
             progress("device loop timed; drop-in latency legs")
             med, p90, b2b = dropin_latency(K, T, local_rank)
             out["control_step_latency_ms"] = med
@@ -736,7 +766,7 @@ def main():
                 "rounding pinned at run time, hostrng.dot2_model); "
                 "numpy_noise_closed_loop: the same in run.py's closed loop (100 ticks after 30). "
                 "ms_per_step is the device-resident loop")
-        if world == 1 and c5:
+        if args.full and world == 1 and c5:
             out["control_step_latency_back_to_back_ms"] = chain_dropin_latency(K, T, local_rank, args.precision)
             progress("NumPy-noise leg")
             out["control_step_latency_numpy_noise_ms"] = chain_dropin_latency(K, T, local_rank, args.precision,
@@ -750,7 +780,7 @@ def main():
                 "numpy_noise: the same with the drop-in's default noise='numpy', the reference's own "
                 "np.random.multivariate_normal stream (NumPy's values and RNG state) drawn on the device every "
                 "call, the next call's beside the step (10 calls after 3). ms_per_step is the device-resident loop")
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             progress("CPU baseline")
             out["cpu_baseline"] = (cpu_baseline_c5(args, window, x0, u, K, T) if c5
                                    else cpu_baseline(args, window, x0, u))

@@ -207,6 +207,18 @@ def test_bench_launches_ranks_itself(monkeypatch):
     assert bench.default_backend(2) == "gloo" and bench.default_backend(1) == "nccl"
 
 
+def test_bench_plain_run_is_the_default(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` asks for none of the legs beside the headline figure and
+    writes no outputs; `--full` and `--dump-outputs DIR` turn them on."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d" and a.cpu_seconds > 0
+
+
 def test_bench_host_cores_is_the_affinity_mask():
     import bench
     assert bench.host_cores() == len(os.sched_getaffinity(0))

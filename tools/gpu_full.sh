@@ -16,8 +16,8 @@ fi
 summ() { python -c "import json,sys;d=json.load(open('$1'));print('$2', 'kernel_us', round(d['kernel_ms']*1e3,2), 'ms_per_step', round(d['ms_per_step'],4), 'frac', round(d['roofline']['frac'],4), 'lat', d.get('control_step_latency_ms'), 'b2b', d.get('control_step_latency_back_to_back_ms'), 'np', d.get('control_step_latency_numpy_noise_ms'), 'lps', d['config'].get('lanes_per_sample'), 'x', d['config'].get('exchange'))"; }
 for W in "c3" "c2" "c5" "c5 --K 16384"; do
   n=$(echo $W | tr ' ' '_' | tr -d '-')
-  timeout -k 10 300 python bench.py --workload $W > $O/bench_$n.json 2> $O/bench_$n.err || { tail -30 $O/bench_$n.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $W > $O/bench_$n.json 2> $O/bench_$n.err || { tail -30 $O/bench_$n.err; exit 1; }
   summ $O/bench_$n.json "$n"
 done
-timeout -k 10 300 python bench.py --gpus 2 --steps 2000 --cpu-seconds 0 > $O/bench_c3_2ranks.json 2> $O/bench_c3_2ranks.err || { tail -30 $O/bench_c3_2ranks.err; exit 1; }
+timeout -k 10 300 python bench.py --full --gpus 2 --steps 2000 --cpu-seconds 0 > $O/bench_c3_2ranks.json 2> $O/bench_c3_2ranks.err || { tail -30 $O/bench_c3_2ranks.err; exit 1; }
 summ $O/bench_c3_2ranks.json c3_2ranks

@@ -8,5 +8,5 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -m gpu -q -x --ti
 rc=$?; echo "gputest rc=$rc"; grep -E "passed|failed" $O/gputest.log | tail -2; [ $rc -eq 0 ] || { grep -E "^FAILED|^E " $O/gputest.log | head -20; exit $rc; }
 timeout -k 10 300 python tools/latency_breakdown.py > $O/latency_breakdown.txt 2>&1 || { tail -5 $O/latency_breakdown.txt; exit 1; }
 cat $O/latency_breakdown.txt
-timeout -k 10 300 python bench.py --cpu-seconds 0 > $O/c3.json 2> $O/c3.err || { tail -5 $O/c3.err; exit 1; }
+timeout -k 10 300 python bench.py --full --cpu-seconds 0 > $O/c3.json 2> $O/c3.err || { tail -5 $O/c3.err; exit 1; }
 python -c "import json;d=json.load(open('$O/c3.json'));print('c3 kernel_us', round(d['kernel_ms']*1e3,2), 'lat', round(d['control_step_latency_ms'],4), 'p90', round(d['control_step_latency_p90_ms'],4), 'b2b', round(d['control_step_latency_back_to_back_ms'],4))"

@@ -11,12 +11,12 @@ rc=$?; echo "world tests rc=$rc"; fatal $rc world
 timeout -k 10 400 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread \
     --ignore=tests/test_gpu_exchange_world.py > "$out/gpu.log" 2>&1
 rc=$?; echo "gpu suite rc=$rc"; tail -3 "$out/gpu.log"; fatal $rc suite
-GPU_MAX_HW_QUEUES=1 timeout -k 10 300 python bench.py --gpus 8 --K 1536 --lps 1 --steps 500 --warmup 20 \
+GPU_MAX_HW_QUEUES=1 timeout -k 10 300 python bench.py --full --gpus 8 --K 1536 --lps 1 --steps 500 --warmup 20 \
     --cpu-seconds 0 > "$out/bench_w8_k1536.json" 2> "$out/bench_w8_k1536.err"
 rc=$?; echo "bench w8 rc=$rc"; fatal $rc bench_w8
-GPU_MAX_HW_QUEUES=1 timeout -k 10 300 python bench.py --gpus 4 --K 1536 --lps 1 --steps 500 --warmup 20 \
+GPU_MAX_HW_QUEUES=1 timeout -k 10 300 python bench.py --full --gpus 4 --K 1536 --lps 1 --steps 500 --warmup 20 \
     --cpu-seconds 0 > "$out/bench_w4_k1536.json" 2> "$out/bench_w4_k1536.err"
 rc=$?; echo "bench w4 rc=$rc"; fatal $rc bench_w4
-timeout -k 10 300 python bench.py --steps 1000 --warmup 100 --cpu-seconds 0 > "$out/bench_c3.json" 2> "$out/bench_c3.err"
+timeout -k 10 300 python bench.py --full --steps 1000 --warmup 100 --cpu-seconds 0 > "$out/bench_c3.json" 2> "$out/bench_c3.err"
 rc=$?; echo "bench c3 rc=$rc"; fatal $rc bench_c3
 exit 0
