@@ -1,5 +1,9 @@
 """RolloutEngine — Python handle on one device context of the HIP engine.
 
+``_Engine`` holds the calls the 2-link arm's ``mppi_*`` and the n-link chain's
+``mppi_chain_*`` ABI share; ``RolloutEngine`` (here) and ``chain.ChainEngine``
+add their config marshalling and what only their ABI has.
+
 PyTorch-ROCm is used only to own device memory and streams: noise buffers,
 per-sample costs, partials and trajectories are torch tensors whose
 ``data_ptr()`` crosses the C ABI (include/mppi_rocm.h).  All work is issued on
@@ -28,89 +32,46 @@ def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def _upload_std(eng, noise, z: torch.Tensor, out: torch.Tensor, perm) -> torch.Event:
-    """RolloutEngine / ChainEngine.upload_std_noise: rows [k_offset, k_offset + K_local) of the (K, T, du)
-    standard normals in the page-locked z, to the device, transformed there, into out (layout `perm` of
-    (K_local, T, du))."""
-    eng._sync_stream()
-    K, T, du = noise.z.shape
-    lo, kl = eng.k_offset, eng.K_local
-    zz = z[:K * T * du].view(K, T, du)[lo:lo + kl]
-    stage = getattr(eng, "_noise_stage", None)
-    if stage is None or tuple(stage.shape) != (kl, T, du):
-        stage = eng._noise_stage = torch.empty((kl, T, du), dtype=torch.float64, device=eng.device)
-    stage.copy_(zz, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record(eng.stream)   # the engine's stream (its device need not be the current one)
-    key = (noise.src.tobytes(), noise.scale.tobytes(), noise.mean.tobytes())
-    if getattr(eng, "_std_key", None) != key:
-        eng._std_key = key
-        eng._std_t = (torch.from_numpy(noise.src).to(eng.device), torch.from_numpy(noise.scale).to(eng.device),
-                      torch.from_numpy(noise.mean).to(eng.device),
-                      bool(np.array_equal(noise.src, np.arange(du))))
-    src, scale, mean, ident = eng._std_t
-    x = stage if ident else stage.index_select(2, src)
-    x = torch.mul(x, scale)          # the np.dot with one nonzero per column: exact products
-    x.add_(mean)                     # x += mean
-    out.copy_(x.permute(*perm))      # transpose + fp64 -> fp32 (round to nearest, as astype)
-    return ev
+class _Engine:
+    """One native context (one device, one shard of samples) of either C ABI: the 2-link arm's ``mppi_*`` or
+    the n-link chain's ``mppi_chain_*`` (include/mppi_rocm.h).  The two differ in the symbol prefix and in the
+    control and state widths (dim_u, dim_x: 2, 4 for the arm; n, 2n for the chain); a subclass marshals its
+    config struct and adds the calls only its ABI has.  Noise layout [T][K_local][dim_u] fp32."""
 
+    # the entry points both ABIs have under their prefix; resolved once at construction into self._c_<name>
+    CALLS = ("ctx_create", "ctx_destroy", "set_stream", "set_step_inputs", "rollout", "merge_partials",
+             "exchange_handle", "exchange_attach", "get_weighted_noise", "get_nominal", "rollout_traj",
+             "wait_outputs", "optimal_traj_host", "noise_philox", "sync")
+    # wait_outputs first follows torch's current stream (the arm's does not: no stream synchronise on its path)
+    WAIT_FOLLOWS_STREAM = False
 
-class RolloutEngine:
-    """Owns one ``mppi_ctx`` (one device, one shard of samples)."""
-
-    def __init__(self, K_local: int, T: int, delta_t: float, param_lambda: float, param_alpha: float,
-                 sigma, stage_cost_weight, terminal_cost_weight, param_exploration: float = 0.0,
-                 arm: ArmParams = ArmParams(), K_total: int | None = None, k_offset: int = 0,
-                 device: int | torch.device | None = None, lanes_per_sample: int = 0,
-                 param_gamma: float | None = None):
+    def __init__(self, prefix: str, dim_u: int, dim_x: int, cfg, K_local: int, T: int, K_total: int | None,
+                 k_offset: int, device: int | torch.device | None):
+        """Create the context from `cfg` (the subclass's config struct; the shard geometry is filled in here)
+        on torch's current stream of `device`."""
         self._lib = N.load()
+        self._prefix, self.dim_u, self.dim_x = prefix, int(dim_u), int(dim_x)
+        for name in self.CALLS:
+            setattr(self, "_c_" + name, getattr(self._lib, prefix + name))
         if device is None:
             device = torch.cuda.current_device()
         self.device = torch.device("cuda", device if isinstance(device, int) else device.index)
         self.K_local, self.T = int(K_local), int(T)
         self.K_total = int(K_total if K_total is not None else K_local)
         self.k_offset = int(k_offset)
-        cfg = N.ConfigC()
         cfg.K_local, cfg.T, cfg.K_total, cfg.k_offset = self.K_local, self.T, self.K_total, self.k_offset
-        cfg.delta_t = float(delta_t)
-        cfg.param_lambda = float(param_lambda)
-        cfg.param_alpha = float(param_alpha)
-        cfg.param_exploration = float(param_exploration)
-        sig = np.asarray(sigma, dtype=np.float64).reshape(2, 2)
-        for i, v in enumerate(sig.ravel()):
-            cfg.sigma[i] = float(v)
-        for i in range(4):
-            cfg.stage_cost_weight[i] = float(stage_cost_weight[i])
-            cfg.terminal_cost_weight[i] = float(terminal_cost_weight[i])
-        for f in ("m1", "m2", "l1", "l2", "lc1", "lc2", "g", "fk_l1", "fk_l2"):
-            setattr(cfg.arm, f, float(getattr(arm, f)))
-        cfg.lanes_per_sample = int(lanes_per_sample)
-        # gamma as given (control.py:45 fixes it at construction); None: lambda (1 - alpha)
-        cfg.param_gamma = float("nan") if param_gamma is None else float(param_gamma)
-        self.sigma = sig
-        self.param_lambda = float(param_lambda)
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream(self.device)
             ctx = C.c_void_p()
-            N.check(self._lib.mppi_ctx_create(C.byref(cfg), self.device.index,
-                                              C.c_void_p(self.stream.cuda_stream), C.byref(ctx)),
-                    "mppi_ctx_create")
+            N.check(self._c_ctx_create(C.byref(cfg), self.device.index, C.c_void_p(self.stream.cuda_stream),
+                                       C.byref(ctx)), prefix + "ctx_create")
         self._ctx = ctx
-        lps, blocks, threads = C.c_int(), C.c_int(), C.c_int()
-        N.check(self._lib.mppi_ctx_info(ctx, C.byref(lps), C.byref(blocks), C.byref(threads)), "mppi_ctx_info")
-        self.lanes_per_sample, self.blocks, self.threads = lps.value, blocks.value, threads.value
-        poll = C.c_int()
-        N.check(self._lib.mppi_ctx_handoff(ctx, C.byref(poll)), "mppi_ctx_handoff")
-        # in-launch hand-off of the workgroup partials: "poll" (tagged granules) or "counter"
-        self.handoff = "poll" if poll.value else "counter"
-        self.partial_len = 2 + 2 * self.T
-        self._weps = np.zeros((self.T, 2))
+        self.partial_len = 2 + self.dim_u * self.T
 
     # -- lifetime -----------------------------------------------------------
     def close(self) -> None:
         if getattr(self, "_ctx", None):
-            self._lib.mppi_ctx_destroy(self._ctx)
+            self._c_ctx_destroy(self._ctx)
             self._ctx = None
         self._noise_stage = None
 
@@ -131,18 +92,18 @@ class RolloutEngine:
         if s.cuda_stream != self.stream.cuda_stream:
             s.wait_stream(self.stream)
             self.stream = s
-            N.check(self._lib.mppi_set_stream(self._ctx, C.c_void_p(s.cuda_stream)), "mppi_set_stream")
+            N.check(self._c_set_stream(self._ctx, C.c_void_p(s.cuda_stream)), self._prefix + "set_stream")
 
     # -- buffers ------------------------------------------------------------
     def new_noise(self) -> torch.Tensor:
-        """Device noise buffer, layout [T][K_local][2] fp32."""
-        return torch.empty((self.T, self.K_local, 2), dtype=torch.float32, device=self.device)
+        """Device noise buffer, layout [T][K_local][dim_u] fp32."""
+        return torch.empty((self.T, self.K_local, self.dim_u), dtype=torch.float32, device=self.device)
 
     def new_partial(self) -> torch.Tensor:
         return torch.empty(self.partial_len, dtype=torch.float64, device=self.device)
 
     def upload_noise(self, eps_kt: np.ndarray, out: torch.Tensor | None = None) -> torch.Tensor:
-        """Reference-order noise (K_local, T, 2) -> device [T][K_local][2] fp32."""
+        """Reference-order noise (K_local, T, dim_u) -> device [T][K_local][dim_u] fp32."""
         out = self.new_noise() if out is None else out
         # the fp64 draw as it is (one pageable copy, the host array free once it returns), then the transpose
         # and the fp64 -> fp32 rounding (to nearest, as NumPy's astype) in one device copy: the host transpose,
@@ -156,32 +117,53 @@ class RolloutEngine:
         return out
 
     def upload_std_noise(self, noise, z: torch.Tensor, out: torch.Tensor) -> torch.Event:
-        """The reference's draw from its standard normals (hostrng.StdNoise `noise`, whose z lives in the
-        page-locked tensor `z`; this shard's K_local rows from k_offset): one DMA, then the transform
+        """The reference's draw from its standard normals (hostrng.StdNoise `noise`, whose (K, T, dim_u) z lives
+        in the page-locked tensor `z`; this shard's K_local rows from k_offset): one DMA, then the transform
         x = z[..., src] * scale + mean as NumPy's (separate fp64 multiply and add: exact, so the values equal
         np.random.multivariate_normal's) and the transpose with the rounding to fp32 (upload_noise).  Returns
         the event after the DMA: z must not be rewritten before it."""
-        return _upload_std(self, noise, z, out, (1, 0, 2))
+        self._sync_stream()
+        K, T, du = noise.z.shape
+        lo, kl = self.k_offset, self.K_local
+        zz = z[:K * T * du].view(K, T, du)[lo:lo + kl]
+        stage = getattr(self, "_noise_stage", None)
+        if stage is None or tuple(stage.shape) != (kl, T, du):
+            stage = self._noise_stage = torch.empty((kl, T, du), dtype=torch.float64, device=self.device)
+        stage.copy_(zz, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(self.stream)   # the engine's stream (its device need not be the current one)
+        key = (noise.src.tobytes(), noise.scale.tobytes(), noise.mean.tobytes())
+        if getattr(self, "_std_key", None) != key:
+            self._std_key = key
+            self._std_t = (torch.from_numpy(noise.src).to(self.device), torch.from_numpy(noise.scale).to(self.device),
+                           torch.from_numpy(noise.mean).to(self.device),
+                           bool(np.array_equal(noise.src, np.arange(du))))
+        src, scale, mean, ident = self._std_t
+        x = stage if ident else stage.index_select(2, src)
+        x = torch.mul(x, scale)          # the np.dot with one nonzero per column: exact products
+        x.add_(mean)                     # x += mean
+        out.copy_(x.permute(1, 0, 2))    # transpose + fp64 -> fp32 (round to nearest, as astype)
+        return ev
 
     # -- the hot path -------------------------------------------------------
     def set_step_inputs(self, x0, window, u=None) -> None:
         self._sync_stream()
-        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).ravel()[:4])
+        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).ravel()[:self.dim_x])
         win = np.ascontiguousarray(np.asarray(window, dtype=np.float64)[:, :4])
         if win.ndim != 2 or win.shape[0] < 1 or win.shape[0] > N.MPPI_SEARCH_LEN:
             raise ValueError("window must have 1..30 rows of [x, y, dq1, dq2]")
         uu = None
         if u is not None:
-            uu = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(self.T, 2))
-        N.check(self._lib.mppi_set_step_inputs(self._ctx, _dptr(x0), _dptr(win), win.shape[0],
-                                               _dptr(uu) if uu is not None else None),
-                "mppi_set_step_inputs")
+            uu = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(self.T, self.dim_u))
+        N.check(self._c_set_step_inputs(self._ctx, _dptr(x0), _dptr(win), win.shape[0],
+                                        _dptr(uu) if uu is not None else None),
+                self._prefix + "set_step_inputs")
         self._keep = (x0, win, uu)  # keep host arrays alive until the async copy ran
 
     def exchange_handle(self, world: int) -> bytes:
         """Allocate this rank's exchange inbox for `world` ranks; its IPC handle (64 B)."""
         buf = C.create_string_buffer(N.MPPI_IPC_HANDLE_BYTES)
-        N.check(self._lib.mppi_exchange_handle(self._ctx, int(world), buf), "mppi_exchange_handle")
+        N.check(self._c_exchange_handle(self._ctx, int(world), buf), self._prefix + "exchange_handle")
         return buf.raw
 
     def exchange_attach(self, rank: int, world: int, handles) -> None:
@@ -189,8 +171,8 @@ class RolloutEngine:
         blob = b"".join(bytes(h) for h in handles)
         if len(blob) != world * N.MPPI_IPC_HANDLE_BYTES:
             raise ValueError("one 64-byte handle per rank")
-        N.check(self._lib.mppi_exchange_attach(self._ctx, int(rank), int(world), C.create_string_buffer(blob, len(blob))),
-                "mppi_exchange_attach")
+        N.check(self._c_exchange_attach(self._ctx, int(rank), int(world), C.create_string_buffer(blob, len(blob))),
+                self._prefix + "exchange_attach")
         self.exchange_world = int(world)
 
     def rollout(self, noise: torch.Tensor, S_out: torch.Tensor | None = None,
@@ -204,66 +186,133 @@ class RolloutEngine:
             assert S_out.dtype == torch.float64 and S_out.numel() >= self.K_local and S_out.device == self.device
         if partial_out is not None:
             assert partial_out.dtype == torch.float64 and partial_out.numel() >= self.partial_len
-        N.check(self._lib.mppi_rollout(self._ctx, C.c_void_p(noise.data_ptr()),
-                                       C.c_void_p(S_out.data_ptr()) if S_out is not None else None,
-                                       C.c_void_p(partial_out.data_ptr()) if partial_out is not None else None,
-                                       (N.MPPI_FLAG_FUSED_UPDATE if fused_update else 0)
-                                       | (N.MPPI_FLAG_EXCHANGE if exchange else 0)
-                                       | (N.MPPI_FLAG_HOST_OUT if host_out else 0)),
-                "mppi_rollout")
+        N.check(self._c_rollout(self._ctx, C.c_void_p(noise.data_ptr()),
+                                C.c_void_p(S_out.data_ptr()) if S_out is not None else None,
+                                C.c_void_p(partial_out.data_ptr()) if partial_out is not None else None,
+                                (N.MPPI_FLAG_FUSED_UPDATE if fused_update else 0)
+                                | (N.MPPI_FLAG_EXCHANGE if exchange else 0)
+                                | (N.MPPI_FLAG_HOST_OUT if host_out else 0)),
+                self._prefix + "rollout")
 
-    def merge(self, partials: torch.Tensor, n: int, fused_update: bool = False, host_out: bool = False) -> None:
+    def merge(self, partials: torch.Tensor, n: int, fused_update: bool = False, flags: int = 0) -> None:
         self._sync_stream()
         assert partials.dtype == torch.float64 and partials.is_contiguous()
         assert partials.numel() >= n * self.partial_len
-        N.check(self._lib.mppi_merge_partials(self._ctx, C.c_void_p(partials.data_ptr()), int(n),
-                                              (N.MPPI_FLAG_FUSED_UPDATE if fused_update else 0)
-                                              | (N.MPPI_FLAG_HOST_OUT if host_out else 0)),
-                "mppi_merge_partials")
+        N.check(self._c_merge_partials(self._ctx, C.c_void_p(partials.data_ptr()), int(n),
+                                       (N.MPPI_FLAG_FUSED_UPDATE if fused_update else 0) | flags),
+                self._prefix + "merge_partials")
 
     def wait_outputs(self, x0=None):
-        """After a host_out launch: (shifted nominal (T, 2) fp64, fp64 optimal trajectory (T, 4)
-        from x0, or None without x0) — mppi_wait_outputs, no stream synchronise."""
-        u_out = np.empty((self.T, 2))
+        """After a host_out launch: (shifted nominal (T, dim_u) fp64, fp64 optimal trajectory (T, dim_x) of the
+        update before its shift from x0, or None without x0) — <prefix>wait_outputs."""
+        if self.WAIT_FOLLOWS_STREAM:
+            self._sync_stream()
+        u_out = np.empty((self.T, self.dim_u))
         traj = None
         xp = None
         if x0 is not None:
-            x = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).ravel()[:4])
-            traj = np.empty((self.T, 4))
+            x = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).ravel()[:self.dim_x])
+            traj = np.empty((self.T, self.dim_x))
             xp = _dptr(x)
-        N.check(self._lib.mppi_wait_outputs(self._ctx, xp, _dptr(u_out), _dptr(traj) if traj is not None else None),
-                "mppi_wait_outputs")
+        N.check(self._c_wait_outputs(self._ctx, xp, _dptr(u_out), _dptr(traj) if traj is not None else None),
+                self._prefix + "wait_outputs")
         return u_out, traj
 
     def weighted_noise(self) -> np.ndarray:
-        """w_eps (T, 2) fp64 of the last rollout / merge (synchronising)."""
+        """w_eps (T, dim_u) fp64 of the last rollout / merge (synchronising)."""
         self._sync_stream()
-        out = np.zeros((self.T, 2))
-        N.check(self._lib.mppi_get_weighted_noise(self._ctx, _dptr(out)), "mppi_get_weighted_noise")
+        out = np.zeros((self.T, self.dim_u))
+        N.check(self._c_get_weighted_noise(self._ctx, _dptr(out)), self._prefix + "get_weighted_noise")
         return out
 
     def nominal(self) -> np.ndarray:
         self._sync_stream()
-        out = np.zeros((self.T, 2))
-        N.check(self._lib.mppi_get_nominal(self._ctx, _dptr(out)), "mppi_get_nominal")
+        out = np.zeros((self.T, self.dim_u))
+        N.check(self._c_get_nominal(self._ctx, _dptr(out)), self._prefix + "get_nominal")
         return out
 
     def trajectories(self, base_u=None, noise: torch.Tensor | None = None, K: int | None = None) -> torch.Tensor:
-        """(K, T, 4) fp32 states of the off-by-one re-roll (control.py:129-145)."""
+        """(K, T, dim_x) fp32 states of the off-by-one re-roll (control.py:129-145)."""
         self._sync_stream()
         K = self.K_local if K is None else int(K)
-        out = torch.empty((K, self.T, 4), dtype=torch.float32, device=self.device)
+        out = torch.empty((K, self.T, self.dim_x), dtype=torch.float32, device=self.device)
         bu = None
         if base_u is not None:
-            bu = np.ascontiguousarray(np.asarray(base_u, dtype=np.float64).reshape(self.T, 2))
+            bu = np.ascontiguousarray(np.asarray(base_u, dtype=np.float64).reshape(self.T, self.dim_u))
         if noise is not None:
             self._check_noise(noise)
-        N.check(self._lib.mppi_rollout_traj(self._ctx, _dptr(bu) if bu is not None else None,
-                                            C.c_void_p(noise.data_ptr()) if noise is not None else None,
-                                            K, C.c_void_p(out.data_ptr())),
-                "mppi_rollout_traj")
+        N.check(self._c_rollout_traj(self._ctx, _dptr(bu) if bu is not None else None,
+                                     C.c_void_p(noise.data_ptr()) if noise is not None else None,
+                                     K, C.c_void_p(out.data_ptr())),
+                self._prefix + "rollout_traj")
         self._keep_traj = bu
         return out
+
+    def optimal_traj_host(self, x0, u_new) -> np.ndarray:
+        """(T, dim_x) fp64 optimal trajectory of control.py:129-134 from the updated, not yet
+        shifted controls u_new (T, dim_u), on the host (<prefix>optimal_traj_host)."""
+        x = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).ravel()[:self.dim_x])
+        un = np.ascontiguousarray(np.asarray(u_new, dtype=np.float64).reshape(self.T, self.dim_u))
+        out = np.empty((self.T, self.dim_x))
+        N.check(self._c_optimal_traj_host(self._ctx, _dptr(x), _dptr(un), _dptr(out)),
+                self._prefix + "optimal_traj_host")
+        return out
+
+    def philox_noise(self, seed: int, step: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+        self._sync_stream()
+        out = self.new_noise() if out is None else out
+        self._check_noise(out)
+        N.check(self._c_noise_philox(self._ctx, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                                     C.c_void_p(out.data_ptr())), self._prefix + "noise_philox")
+        return out
+
+    def synchronize(self) -> None:
+        N.check(self._c_sync(self._ctx), self._prefix + "sync")
+
+    def _check_noise(self, noise: torch.Tensor) -> None:
+        shape = (self.T, self.K_local, self.dim_u)
+        if (noise.dtype != torch.float32 or not noise.is_contiguous() or noise.device != self.device
+                or tuple(noise.shape) != shape):
+            raise ValueError(f"noise must be a contiguous fp32 {shape} tensor on {self.device}")
+
+
+class RolloutEngine(_Engine):
+    """Owns one ``mppi_ctx`` (one device, one shard of samples)."""
+
+    def __init__(self, K_local: int, T: int, delta_t: float, param_lambda: float, param_alpha: float,
+                 sigma, stage_cost_weight, terminal_cost_weight, param_exploration: float = 0.0,
+                 arm: ArmParams = ArmParams(), K_total: int | None = None, k_offset: int = 0,
+                 device: int | torch.device | None = None, lanes_per_sample: int = 0,
+                 param_gamma: float | None = None):
+        cfg = N.ConfigC()
+        cfg.delta_t = float(delta_t)
+        cfg.param_lambda = float(param_lambda)
+        cfg.param_alpha = float(param_alpha)
+        cfg.param_exploration = float(param_exploration)
+        sig = np.asarray(sigma, dtype=np.float64).reshape(2, 2)
+        for i, v in enumerate(sig.ravel()):
+            cfg.sigma[i] = float(v)
+        for i in range(4):
+            cfg.stage_cost_weight[i] = float(stage_cost_weight[i])
+            cfg.terminal_cost_weight[i] = float(terminal_cost_weight[i])
+        for f in ("m1", "m2", "l1", "l2", "lc1", "lc2", "g", "fk_l1", "fk_l2"):
+            setattr(cfg.arm, f, float(getattr(arm, f)))
+        cfg.lanes_per_sample = int(lanes_per_sample)
+        # gamma as given (control.py:45 fixes it at construction); None: lambda (1 - alpha)
+        cfg.param_gamma = float("nan") if param_gamma is None else float(param_gamma)
+        self.sigma = sig
+        self.param_lambda = float(param_lambda)
+        super().__init__("mppi_", 2, 4, cfg, K_local, T, K_total, k_offset, device)
+        lps, blocks, threads = C.c_int(), C.c_int(), C.c_int()
+        N.check(self._lib.mppi_ctx_info(self._ctx, C.byref(lps), C.byref(blocks), C.byref(threads)), "mppi_ctx_info")
+        self.lanes_per_sample, self.blocks, self.threads = lps.value, blocks.value, threads.value
+        poll = C.c_int()
+        N.check(self._lib.mppi_ctx_handoff(self._ctx, C.byref(poll)), "mppi_ctx_handoff")
+        # in-launch hand-off of the workgroup partials: "poll" (tagged granules) or "counter"
+        self.handoff = "poll" if poll.value else "counter"
+
+    def merge(self, partials: torch.Tensor, n: int, fused_update: bool = False, host_out: bool = False) -> None:
+        super().merge(partials, n, fused_update, N.MPPI_FLAG_HOST_OUT if host_out else 0)   # host_out: the arm only
 
     def optimal_traj(self, out: torch.Tensor | None = None) -> torch.Tensor:
         """(T, 4) fp32 optimal trajectory (control.py:129-134) from the controls of the
@@ -369,23 +418,6 @@ class RolloutEngine:
         N.check(self._lib.mppi_debug_dropin_times(self._ctx, _dptr(out)), "mppi_debug_dropin_times")
         return out
 
-    def optimal_traj_host(self, x0, u_new) -> np.ndarray:
-        """(T, 4) fp64 optimal trajectory of control.py:129-134 from the updated, not yet
-        shifted controls u_new (T, 2), on the host (mppi_optimal_traj_host)."""
-        x = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).ravel()[:4])
-        un = np.ascontiguousarray(u_new, dtype=np.float64).reshape(self.T, 2)
-        out = np.empty((self.T, 4))
-        N.check(self._lib.mppi_optimal_traj_host(self._ctx, _dptr(x), _dptr(un), _dptr(out)), "mppi_optimal_traj_host")
-        return out
-
-    def philox_noise(self, seed: int, step: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
-        self._sync_stream()
-        out = self.new_noise() if out is None else out
-        self._check_noise(out)
-        N.check(self._lib.mppi_noise_philox(self._ctx, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
-                                            C.c_void_p(out.data_ptr())), "mppi_noise_philox")
-        return out
-
     def nearest_slots(self, noise: torch.Tensor, K: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Tests: the window slot the rollout picks for each of the first K samples at
         every step (_get_nearest_waypoint in _c, control.py:176-180, 205-215), and the
@@ -400,14 +432,6 @@ class RolloutEngine:
                 "mppi_debug_nearest")
         self.synchronize()
         return slot.cpu().numpy(), pos.cpu().numpy()
-
-    def synchronize(self) -> None:
-        N.check(self._lib.mppi_sync(self._ctx), "mppi_sync")
-
-    def _check_noise(self, noise: torch.Tensor) -> None:
-        if (noise.dtype != torch.float32 or not noise.is_contiguous() or noise.device != self.device
-                or tuple(noise.shape) != (self.T, self.K_local, 2)):
-            raise ValueError(f"noise must be a contiguous fp32 {(self.T, self.K_local, 2)} tensor on {self.device}")
 
 
 def readback_workers() -> int:

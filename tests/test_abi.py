@@ -37,6 +37,22 @@ def test_library_loads_and_exports_every_symbol():
     assert set(declared_functions()) <= exported
 
 
+def test_engine_base_dispatch_names_exist_under_both_prefixes():
+    """Every call engine._Engine resolves from prefix + name is exported, with a signature, by the 2-link
+    ABI (mppi_<name>) and by the chain's (mppi_chain_<name>): a typo in the table fails here, without a GPU."""
+    from mppi_robotarm_amd import _native
+    from mppi_robotarm_amd.engine import _Engine
+    if not os.path.exists(_native.LIB_PATH):
+        from mppi_robotarm_amd.build import build_native
+        build_native()
+    lib = _native.open_library(_native.LIB_PATH)
+    assert len(_Engine.CALLS) == len(set(_Engine.CALLS)) >= 15
+    for name in _Engine.CALLS:
+        for prefix in ("mppi_", "mppi_chain_"):
+            assert prefix + name in _native.EXPORTS, prefix + name
+            assert getattr(lib, prefix + name).argtypes is not None, prefix + name
+
+
 def test_struct_layout_matches_header(tmp_path):
     from mppi_robotarm_amd import _native as N
     probe = tmp_path / "probe.c"

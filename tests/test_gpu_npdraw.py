@@ -213,15 +213,18 @@ def test_queued_draw_is_dropped_when_numpy_state_or_sigma_changes():
     assert _same_state(st_a, st_b)
 
 
-def _chain_loop(device_draw: bool, lam: float, ticks=3, K=4096, T=16):
+def _chain_loop(device_draw: bool, lam: float, ticks=3, K=4096, T=16, between=None, precision="auto"):
     from mppi_robotarm_amd.chain import CHAIN7_X0, ChainMPPIController, gravity_torque
     from conftest import load_paths
     c = ChainMPPIController(0.006, load_paths()["xydq_circle"], T, K, param_lambda=lam, device=0,
-                            u_init=gravity_torque(CHAIN7_X0[:7]), numpy_noise_on_device=device_draw)
+                            u_init=gravity_torque(CHAIN7_X0[:7]), numpy_noise_on_device=device_draw,
+                            precision=precision)
     np.random.seed(4)
     out, precs, first = [], [], []
     for i in range(ticks):
         c.prev_waypoints_idx = 0
+        if between is not None:
+            between(i, c)
         first.append("f64" if c._spread else "f32")   # the engine this call's draw goes to first
         u0, u_seq, opt, _ = c.calc_control_input(CHAIN7_X0)
         out.append((u_seq.copy(), opt.copy()))
@@ -245,6 +248,37 @@ def test_chain_controller_device_draw_equals_host_draw(lam):
     assert hits == want, "every call whose first engine is the last call's uses the draw queued beside that step"
     assert precs == precs_b
     assert lam < 1e4 or "f64" in precs
+    for (ua, oa), (ub, ob) in zip(a, b):
+        np.testing.assert_array_equal(ua, ub)
+        np.testing.assert_array_equal(oa, ob)
+    assert _same_state(st_a, st_b)
+
+
+def test_chain_queued_draw_is_dropped_when_numpy_state_or_sigma_changes():
+    """The chain's counterpart of test_queued_draw_is_dropped_when_numpy_state_or_sigma_changes (the same
+    controller_base code): K = 4096, T = 16, seven links (458 752 normals, above hostrng._MIN_NORMALS) at
+    lambda = 100, every step fp32 on one engine.  The caller's own draws, a reseed and a new diagonal Sigma
+    between calls give the host draw's steps and state bit for bit; the queued draw is used at calls 3, 5 and
+    7 only.  precision="f32" keeps the steps on one engine: under "auto" the weights of call 4 (the noise after
+    np.random.seed(7)) spread, its step is run again in fp64 and call 5 starts on the fp64 engine, where the
+    draw queued beside call 4 is not (test_chain_controller_device_draw_equals_host_draw covers that switch)."""
+    from mppi_robotarm_amd import hostrng
+    from mppi_robotarm_amd.chain import CHAIN7_SIGMA
+    assert 4096 * 16 * 7 >= hostrng._MIN_NORMALS
+
+    def between(i, c):
+        if i == 1:
+            np.random.rand(3)                               # the caller consumes the stream
+        elif i == 3:
+            np.random.seed(7)
+        elif i == 5:
+            c.Sigma = CHAIN7_SIGMA * 2.0                    # another plan (and another engine key)
+    a, st_a, used, precs, (hits, _) = _chain_loop(True, 100.0, ticks=7, between=between, precision="f32")
+    b, st_b, _, precs_b, _ = _chain_loop(False, 100.0, ticks=7, between=between, precision="f32")
+    assert used, "the chain controller did not take the device draw"
+    assert precs == precs_b == ["f32"] * 7
+    assert hits == 3, "used at calls 3, 5 and 7 only"
+    assert len(a) == len(b) == 7
     for (ua, oa), (ub, ob) in zip(a, b):
         np.testing.assert_array_equal(ua, ub)
         np.testing.assert_array_equal(oa, ob)
