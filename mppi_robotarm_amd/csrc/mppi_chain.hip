@@ -1330,16 +1330,12 @@ struct mppi_chain_ctx {
     int device = 0, n = 0;
     hipStream_t stream = nullptr;
     int nblocks = 0;
-    bool poll = false;
+    mppi_host::Handoff hand;       // hand-off form, its buffers and the time-out words
     ChainConst kc;
     ChainStep* d_step = nullptr;   // [2] ping-pong
     int cur = 0;
     ChainStep* h_step = nullptr;   // pinned staging
     hipEvent_t staged = nullptr;
-    double* d_slab = nullptr;
-    double* d_gslab = nullptr;
-    unsigned* d_counter = nullptr;
-    unsigned* d_epoch = nullptr;
     unsigned long long* d_runmin = nullptr;   // running minimum of the workgroups' rho_b (ord_key), ~0 between launches
     double* d_weps = nullptr;
     double* h_buf = nullptr;
@@ -1358,35 +1354,28 @@ struct mppi_chain_ctx {
     double h_pub[kCMaxVals] = {};
     bool f64 = false;              // cfg.precision == 1
     int lps = 1;                   // lanes per sample: 1, or 4 (fp32 rollout at small K)
-    unsigned* h_tmo = nullptr;
-    unsigned* d_tmo = nullptr;
     unsigned long long* d_dbg = nullptr;
-    // node-level exchange (mppi_chain_exchange_*), as in mppi_ctx
-    XDesc xd{};
-    void* d_inbox = nullptr;
-    double* d_xrow = nullptr;
-    unsigned* d_xepoch = nullptr;
-    int xworld_alloc = 0;
-    void* xopened[kMaxWorld] = {};
+    mppi_host::Exchange ex;        // node-level exchange (mppi_chain_exchange_*)
 };
 
 namespace {
 
-using mppi_host::exchange_timeout_ticks;
 using mppi_host::fail;
+using mppi_host::launch_check;
 
 template <int N, bool P, bool F64, int LPS>
 void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise, double* S, double* part, ChainStep* nxt,
                     unsigned flags, int* slots = nullptr) {
+    const mppi_host::Handoff& h = c->hand;
     if (slots) {   // the debug instance: identical arithmetic, plus the slot stores
         if constexpr (N == kCDebugN)
             hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, true>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc,
-                               cur, c->d_dyn, noise, S, c->d_slab, c->d_gslab, c->d_counter, part, c->d_weps, nxt, flags,
-                               c->xd, c->d_epoch, c->d_tmo, c->d_runmin, reinterpret_cast<unsigned long long*>(slots));
+                               cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags,
+                               c->ex.xd, h.d_epoch, h.d_tmo, c->d_runmin, reinterpret_cast<unsigned long long*>(slots));
         return;
     }
     hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc, cur, c->d_dyn,
-                       noise, S, c->d_slab, c->d_gslab, c->d_counter, part, c->d_weps, nxt, flags, c->xd, c->d_epoch, c->d_tmo,
+                       noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags, c->ex.xd, h.d_epoch, h.d_tmo,
                        c->d_runmin, c->d_dbg);
 }
 
@@ -1411,26 +1400,61 @@ int chain_auto_lps(int K_local, bool f64) {
 }
 
 int check_tmo(mppi_chain_ctx* c) {
-    // tmo[0]: a local hand-off gave up (kTmoLocal); tmo[1]: the exchange's verdict bits (mppi_device.h)
-    const unsigned v = c->h_tmo ? __atomic_load_n(c->h_tmo, __ATOMIC_ACQUIRE) | __atomic_load_n(c->h_tmo + 1, __ATOMIC_ACQUIRE)
-                                : 0u;
-    if (!v) return MPPI_OK;
-    c->h_tmo[0] = c->h_tmo[1] = 0;
-    if (v == kTmoExchange) {   // as the 2-link engine's check_timeout: the nominal before the launch
+    unsigned v;
+    const int rc = c->hand.take_timeout(&v);
+    if (v == kTmoExchange) {
+        // every rank of the step reports it and none applied the update: back to the nominal before the launch
         if (c->x_flipped) c->cur ^= 1;
         c->x_flipped = false;
         c->upd_valid = false;
         c->pub_valid = false;
         c->out_posted = false;
-        return fail(MPPI_E_EXCHANGE, "multi-GPU exchange: a rank's row did not arrive within the bound on every "
-                                     "rank of this step; no rank applied the update (run the step again)");
+    } else if (v & kTmoLocal) {
+        // an aborted merge left the running minimum set: clear it for the next launch
+        (void)hipMemsetAsync(c->d_runmin, 0xFF, sizeof(unsigned long long), c->stream);
     }
-    // an aborted merge left the running minimum set: clear it for the next launch
-    if (v & kTmoLocal) (void)hipMemsetAsync(c->d_runmin, 0xFF, sizeof(unsigned long long), c->stream);
-    if (v & kTmoSplit)
-        return fail(MPPI_E_HIP, "multi-GPU exchange: this rank had every row but not every rank's verdict within "
-                                "the bound; other ranks may have applied the step, so it cannot be re-run");
-    return fail(MPPI_E_HIP, "in-launch hand-off timed out (workgroups not co-resident?); results invalid");
+    return rc;
+}
+
+// The device side of mppi_chain_ctx_create: the hand-off form from the rollout kernel's occupancy, then
+// every buffer (on an error the caller destroys the half-built context).
+int alloc(mppi_chain_ctx* c) {
+    HIP_TRY(hipSetDevice(c->device));
+    int ncu = 0, per_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+#define MPPI_OCC(N)                                                                                          \
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(                                                      \
+        &per_cu,                                                                                             \
+        c->f64 ? (const void*)chain_rollout_kernel<N, true, true, 1>                                          \
+               : (c->lps == 4 ? (const void*)chain_rollout_kernel<N, true, false, 4>                          \
+                              : (const void*)chain_rollout_kernel<N, true, false, 1>),                        \
+        kCT, 0)
+    MPPI_CHAIN_DISPATCH(c->n, MPPI_OCC)
+#undef MPPI_OCC
+    // behind the counters: the per-CU ticket words of the issue fairness (mppi_device.h)
+    if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + c->cfg.T * c->n, kCuSlots)) return rc;
+    c->kc.acquire = c->hand.acquire;
+    c->kc.cu_off = (int)c->hand.extra_off;
+    c->kc.fair = c->nblocks > ncu ? 1 : 0;
+    HIP_TRY(hipMalloc(&c->d_step, 2 * sizeof(ChainStep)));
+    HIP_TRY(hipMalloc(&c->d_runmin, 256));
+    HIP_TRY(hipMemset(c->d_runmin, 0xFF, 256));
+    HIP_TRY(hipMalloc(&c->d_weps, (kCMaxVals + 1) * sizeof(double)));
+    HIP_TRY(hipMalloc(&c->d_base, kCMaxVals * sizeof(float)));
+    HIP_TRY(hipMalloc(&c->d_dyn, kDynF64Off * sizeof(float) + sizeof(c->h_dynd)));
+    HIP_TRY(hipMemcpy(c->d_dyn + kDynF64Off, c->h_dynd, sizeof(c->h_dynd), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_dyn, c->kc.dyn, sizeof(c->kc.dyn), hipMemcpyHostToDevice));
+    HIP_TRY(hipHostMalloc(&c->h_step, sizeof(ChainStep), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&c->h_buf, (kCMaxVals + kCMax) * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&c->h_base, kCMaxVals * sizeof(float), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&c->h_out, (kCMaxVals + kCMax + 1) * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&c->staged, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->out_ev, hipEventDisableTiming));
+    HIP_TRY(hipMemset(c->d_step, 0, 2 * sizeof(ChainStep)));
+    HIP_TRY(hipMemset(c->d_weps, 0, (kCMaxVals + 1) * sizeof(double)));
+    HIP_TRY(hipDeviceSynchronize());
+    memset(c->h_step, 0, sizeof(ChainStep));
+    return MPPI_OK;
 }
 
 }  // namespace
@@ -1452,9 +1476,7 @@ int mppi_chain_ctx_create(const mppi_chain_config* cfg, int device, void* stream
     if (cfg->T < 1 || cfg->T > MPPI_MAX_T) return fail(MPPI_E_ARG, "T must be in [1, 128]");
     if (cfg->T * n + 1 > kCMaxCh * kCT) return fail(MPPI_E_ARG, "T * n too large");
     if (cfg->precision != 0 && cfg->precision != 1) return fail(MPPI_E_ARG, "precision must be 0 (fp32) or 1 (fp64)");
-    if (cfg->K_local < 1 || cfg->K_total < cfg->K_local || cfg->k_offset < 0 ||
-        cfg->k_offset + (long long)cfg->K_local > cfg->K_total)
-        return fail(MPPI_E_ARG, "bad sample geometry (K_local, K_total, k_offset)");
+    if (int rc = mppi_host::check_sample_geometry(cfg->K_local, cfg->K_total, cfg->k_offset)) return rc;
     if ((long long)cfg->K_local * cfg->T * n >= (1LL << 31)) return fail(MPPI_E_ARG, "too many samples");
     // Sigma: symmetric positive definite (Cholesky), inverse for the control cost
     double Lc[kCMax][kCMax] = {}, Si[kCMax * kCMax] = {};
@@ -1511,41 +1533,13 @@ int mppi_chain_ctx_create(const mppi_chain_config* cfg, int device, void* stream
     c->nblocks = (int)(((long long)cfg->K_local * c->lps + kCT - 1) / kCT);
     ChainConst& k = c->kc;
     memset(&k, 0, sizeof(k));
-    k.K_local = cfg->K_local;
-    k.T = cfg->T;
-    k.k_offset = cfg->k_offset;
-    {
-        const double thr = (1.0 - cfg->param_exploration) * (double)cfg->K_total;  // control.py:98
-        long long kx = thr <= 0.0 ? 0 : (long long)ceil(thr);
-        if (kx > cfg->K_total) kx = cfg->K_total;
-        k.k_exploit = (int)kx;
-    }
-    k.nblocks = c->nblocks;
+    mppi_host::set_common_consts(k, *cfg, c->nblocks);
     k.n = n;
     const mppi_chain_params& P = cfg->chain;
-    float* dyn = k.dyn;
-    for (int a = 0; a < kCMax; ++a) dyn[kOffDd + a] = 1.f;   // pad rows
-    for (int a = 0; a < n; ++a) {
-        double tail = 0.0;
-        for (int q = a + 1; q < n; ++q) tail += P.m[q];
-        const double mu_aa = P.m[a] * P.lc[a] * P.lc[a] + P.l[a] * P.l[a] * tail;
-        const double Jn = a + 1 < n ? P.J[a + 1] : 0.0;
-        dyn[kOffL + a] = (float)P.l[a];
-        dyn[kOffNu + a] = (float)(P.m[a] * P.lc[a] + P.l[a] * tail);
-        dyn[kOffDd + a] = (float)(mu_aa + P.I[a] + P.J[a] + Jn);
-        dyn[kOffJ + 2 * a + ((a + 1) & 1)] = (float)(-Jn);   // row a+1 within its pair
-        dyn[kOffDamp + a] = (float)P.b[a];
-        dyn[kOffFk + a] = (float)P.fk[a];
-    }
-    for (int i = 0; i < 4; ++i) {
-        dyn[kOffSw + i] = (float)(cfg->stage_cost_weight[i] * 10000.0);     // control.py:185
-        dyn[kOffTw + i] = (float)(cfg->terminal_cost_weight[i] * 10000.0);  // control.py:198
-    }
-    dyn[kOffDt] = (float)cfg->delta_t;
-    dyn[kOffG] = (float)P.g;
-    // the fp64 rollout's constants: the same layout, unrounded
-    double dynd[kCDyn] = {};
-    for (int a = 0; a < kCMax; ++a) dynd[kOffDd + a] = 1.0;
+    // the packed constants in fp64 (the fp64 rollout, the host's optimal trajectory); the fp32 rollout's
+    // table is the same layout rounded entry by entry
+    double* dynd = c->h_dynd;
+    for (int a = 0; a < kCMax; ++a) dynd[kOffDd + a] = 1.0;   // pad rows
     for (int a = 0; a < n; ++a) {
         double tail = 0.0;
         for (int q = a + 1; q < n; ++q) tail += P.m[q];
@@ -1553,84 +1547,25 @@ int mppi_chain_ctx_create(const mppi_chain_config* cfg, int device, void* stream
         dynd[kOffL + a] = P.l[a];
         dynd[kOffNu + a] = P.m[a] * P.lc[a] + P.l[a] * tail;
         dynd[kOffDd + a] = P.m[a] * P.lc[a] * P.lc[a] + P.l[a] * P.l[a] * tail + P.I[a] + P.J[a] + Jn;
-        dynd[kOffJ + 2 * a + ((a + 1) & 1)] = -Jn;
+        dynd[kOffJ + 2 * a + ((a + 1) & 1)] = -Jn;   // row a+1 within its pair
         dynd[kOffDamp + a] = P.b[a];
         dynd[kOffFk + a] = P.fk[a];
     }
     for (int i = 0; i < 4; ++i) {
-        dynd[kOffSw + i] = cfg->stage_cost_weight[i] * 10000.0;
-        dynd[kOffTw + i] = cfg->terminal_cost_weight[i] * 10000.0;
+        dynd[kOffSw + i] = cfg->stage_cost_weight[i] * 10000.0;     // control.py:185
+        dynd[kOffTw + i] = cfg->terminal_cost_weight[i] * 10000.0;  // control.py:198
     }
     dynd[kOffDt] = cfg->delta_t;
     dynd[kOffG] = P.g;
-    memcpy(c->h_dynd, dynd, sizeof(dynd));
-    k.lambda = cfg->param_lambda;
-    k.inv_lambda = 1.0 / cfg->param_lambda;
-    // control.py:45 fixes gamma at construction; the caller passes it as given (NaN: lambda (1 - alpha))
-    k.gamma = isnan(cfg->param_gamma) ? cfg->param_lambda * (1.0 - cfg->param_alpha) : cfg->param_gamma;
+    for (int i = 0; i < kCDyn; ++i) k.dyn[i] = (float)dynd[i];
     for (int i = 0; i < n * n; ++i) k.sig_inv[i] = Si[i];
 
-    auto cleanup_fail = [&](int rc) {
-        mppi_chain_ctx_destroy(c);
-        return rc;
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess)
-        return cleanup_fail(fail(MPPI_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)));
-    int ncu = 0, per_cu = 0;
-    if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess)
-        return cleanup_fail(fail(MPPI_E_HIP, std::string("device attributes: ") + hipGetErrorString(e)));
-#define MPPI_OCC(N)                                                                                          \
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(                                                      \
-        &per_cu,                                                                                             \
-        c->f64 ? (const void*)chain_rollout_kernel<N, true, true, 1>                                          \
-               : (c->lps == 4 ? (const void*)chain_rollout_kernel<N, true, false, 4>                          \
-                              : (const void*)chain_rollout_kernel<N, true, false, 1>),                        \
-        kCT, 0)
-    MPPI_CHAIN_DISPATCH(n, MPPI_OCC)
-#undef MPPI_OCC
-    c->poll = per_cu >= 1 && c->nblocks <= ncu;
-    if (const char* ev = getenv("MPPI_HANDOFF")) {
-        if (!strcmp(ev, "counter")) c->poll = false;
-    }
-    k.acquire = (!c->poll && c->nblocks > ncu) ? 1 : 0;
-    const size_t val = c->poll ? 16 : sizeof(double);
-    const int stride = 2 + cfg->T * n;
-    const size_t slab = (size_t)c->nblocks * stride * val;
-    const int ngroups = (c->nblocks + kGroup - 1) / kGroup;
-    const size_t gslab = (size_t)ngroups * stride * val;
-    const size_t cu_off = (((size_t)(ngroups + 2) * sizeof(unsigned) + 255) & ~(size_t)255) / sizeof(unsigned);
-    const size_t ctr_bytes = (cu_off + kCuSlots) * sizeof(unsigned);
-    c->kc.cu_off = (int)cu_off;
-    c->kc.fair = c->nblocks > ncu ? 1 : 0;
     for (int i = 0; i < n; ++i)
         for (int j = 0; j <= i; ++j) c->chol.L[i * kCMax + j] = (float)(Lc[i][j] * kBoxMullerScale);   // box_muller's constant
-    if ((e = hipMalloc(&c->d_step, 2 * sizeof(ChainStep))) != hipSuccess ||
-        (e = hipMalloc(&c->d_slab, slab)) != hipSuccess || (e = hipMalloc(&c->d_gslab, gslab)) != hipSuccess ||
-        (e = hipMalloc(&c->d_counter, ctr_bytes)) != hipSuccess ||
-        (e = hipMalloc(&c->d_runmin, 256)) != hipSuccess || (e = hipMemset(c->d_runmin, 0xFF, 256)) != hipSuccess ||
-        (e = hipMalloc(&c->d_weps, (kCMaxVals + 1) * sizeof(double))) != hipSuccess ||
-        (e = hipMalloc(&c->d_base, kCMaxVals * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc(&c->d_dyn, kDynF64Off * sizeof(float) + sizeof(dynd))) != hipSuccess ||
-        (e = hipMemcpy(c->d_dyn + kDynF64Off, dynd, sizeof(dynd), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_step, sizeof(ChainStep), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_buf, (kCMaxVals + kCMax) * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_base, kCMaxVals * sizeof(float), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_tmo, 256, hipHostMallocMapped)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void**)&c->d_tmo, c->h_tmo, 0)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->staged, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->out_ev, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_out, (kCMaxVals + kCMax + 1) * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipMemset(c->d_counter, 0, ctr_bytes)) != hipSuccess || (e = hipMemset(c->d_slab, 0, slab)) != hipSuccess ||
-        (e = hipMemset(c->d_gslab, 0, gslab)) != hipSuccess ||
-        (e = hipMemset(c->d_step, 0, 2 * sizeof(ChainStep))) != hipSuccess ||
-        (e = hipMemset(c->d_weps, 0, (kCMaxVals + 1) * sizeof(double))) != hipSuccess ||
-        (e = hipMemcpy(c->d_dyn, k.dyn, sizeof(k.dyn), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipDeviceSynchronize()) != hipSuccess)
-        return cleanup_fail(fail(MPPI_E_HIP, std::string("allocation: ") + hipGetErrorString(e)));
-    memset(c->h_step, 0, sizeof(ChainStep));
-    c->h_tmo[0] = c->h_tmo[1] = 0;
-    c->d_epoch = c->d_counter + ngroups + 1;
+    if (int rc = alloc(c)) {
+        mppi_chain_ctx_destroy(c);
+        return rc;
+    }
     *out = c;
     return MPPI_OK;
 }
@@ -1640,24 +1575,17 @@ void mppi_chain_ctx_destroy(mppi_chain_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipDeviceSynchronize();
     (void)hipFree(c->d_step);
-    (void)hipFree(c->d_slab);
-    (void)hipFree(c->d_gslab);
-    (void)hipFree(c->d_counter);
+    c->hand.release();
     (void)hipFree(c->d_runmin);
     (void)hipFree(c->d_weps);
     (void)hipFree(c->d_base);
     (void)hipFree(c->d_dyn);
-    for (void* p : c->xopened)
-        if (p) (void)hipIpcCloseMemHandle(p);
-    (void)hipFree(c->d_inbox);
-    (void)hipFree(c->d_xrow);
-    (void)hipFree(c->d_xepoch);
+    c->ex.release();
     if (c->h_step) (void)hipHostFree(c->h_step);
     if (c->h_buf) (void)hipHostFree(c->h_buf);
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->out_ev) (void)hipEventDestroy(c->out_ev);
     if (c->h_base) (void)hipHostFree(c->h_base);
-    if (c->h_tmo) (void)hipHostFree(c->h_tmo);
     if (c->staged) (void)hipEventDestroy(c->staged);
     delete c;
 }
@@ -1673,7 +1601,7 @@ int mppi_chain_ctx_info(const mppi_chain_ctx* c, int* blocks, int* threads, int*
     if (lanes_per_sample) *lanes_per_sample = c->lps;
     if (blocks) *blocks = c->nblocks;
     if (threads) *threads = kCT;
-    if (poll) *poll = c->poll ? 1 : 0;
+    if (poll) *poll = c->hand.poll ? 1 : 0;
     return MPPI_OK;
 }
 
@@ -1681,27 +1609,9 @@ int mppi_chain_set_step_inputs(mppi_chain_ctx* c, const double* x0, const double
     if (!c || !x0 || !window) return fail(MPPI_E_ARG, "null argument");
     if (W < 1 || W > MPPI_SEARCH_LEN) return fail(MPPI_E_ARG, "window rows must be in [1, 30]");
     const int n = c->n, T = c->cfg.T;
-    if (hipEventSynchronize(c->staged) != hipSuccess) return fail(MPPI_E_HIP, "staging event");
+    HIP_TRY(hipEventSynchronize(c->staged));
     ChainStep* h = c->h_step;
-    double cx = 0.0, cy = 0.0;
-    for (int j = 0; j < W; ++j) {
-        cx += window[4 * j];
-        cy += window[4 * j + 1];
-    }
-    cx /= W;
-    cy /= W;
-    for (int j = 0; j < kSlots; ++j) {
-        if (j < W) {
-            const double* r = window + 4 * j;
-            h->win[j] = make_float4((float)r[0], (float)r[1], (float)r[2], (float)r[3]);
-            const double rx = r[0] - cx, ry = r[1] - cy;
-            h->key[j] = make_float4((float)(-2.0 * rx), (float)(-2.0 * ry), (float)(rx * rx + ry * ry), 0.f);
-        } else {
-            h->win[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            h->key[j] = make_float4(0.f, 0.f, kPadKey, 0.f);
-        }
-    }
-    h->ctr = make_float4((float)cx, (float)cy, (float)W, 0.f);
+    mppi_host::stage_window(window, W, h->win, h->key, &h->ctr);
     for (int a = 0; a < 2 * kCMax; ++a) h->x0[a] = a < 2 * n ? (float)x0[a] : 0.f;
     // fp64 rollout: x0 as [q(n), dq(n)] and the window rows unrounded
     for (int a = 0; a < 2 * kCMax; ++a) h->x0d[a] = a < 2 * n ? x0[a] : 0.0;
@@ -1731,11 +1641,9 @@ int mppi_chain_set_step_inputs(mppi_chain_ctx* c, const double* x0, const double
         c->upd_valid = false;   // the block now holds the staged nominal, not a fused update's output
         c->pub_valid = false;
     }
-    if (hipMemcpyAsync(c->d_step + (c->cur ^ 1), h, offsetof(ChainStep, ua), hipMemcpyHostToDevice, c->stream) !=
-            hipSuccess ||
-        hipMemcpyAsync(c->d_step + c->cur, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipEventRecord(c->staged, c->stream) != hipSuccess)
-        return fail(MPPI_E_HIP, "step input upload");
+    HIP_TRY(hipMemcpyAsync(c->d_step + (c->cur ^ 1), h, offsetof(ChainStep, ua), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_step + c->cur, h, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->staged, c->stream));
     return MPPI_OK;
 }
 
@@ -1749,25 +1657,24 @@ int chain_rollout(mppi_chain_ctx* c, const float* noise_dev, double* S_dev, doub
     if ((flags & MPPI_FLAG_FUSED_UPDATE) && c->cfg.T < 5)
         return fail(MPPI_E_ARG, "device median filter needs T >= 5 (use the host update)");
     if (flags & MPPI_FLAG_EXCHANGE) {
-        if (c->xd.world < 1) return fail(MPPI_E_ARG, "MPPI_FLAG_EXCHANGE before mppi_chain_exchange_attach");
+        if (c->ex.xd.world < 1) return fail(MPPI_E_ARG, "MPPI_FLAG_EXCHANGE before mppi_chain_exchange_attach");
         if (partial_dev) return fail(MPPI_E_ARG, "MPPI_FLAG_EXCHANGE merges on device: no partial_out");
-        partial_dev = c->d_xrow;
+        partial_dev = c->ex.d_xrow;
     }
     const ChainStep* cur = c->d_step + c->cur;
     ChainStep* nxt = c->d_step + (c->cur ^ 1);
 #define MPPI_L(N)                                                                       \
     if (c->f64) {                                                                       \
-        if (c->poll) launch_rollout<N, true, true, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
+        if (c->hand.poll) launch_rollout<N, true, true, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
         else launch_rollout<N, false, true, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
     } else if (c->lps == 4) {                                                           \
-        if (c->poll) launch_rollout<N, true, false, 4>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
+        if (c->hand.poll) launch_rollout<N, true, false, 4>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
         else launch_rollout<N, false, false, 4>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
-    } else if (c->poll) launch_rollout<N, true, false, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
+    } else if (c->hand.poll) launch_rollout<N, true, false, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
     else launch_rollout<N, false, false, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots)
     MPPI_CHAIN_DISPATCH(c->n, MPPI_L)
 #undef MPPI_L
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MPPI_E_HIP, std::string("chain_rollout_kernel: ") + hipGetErrorString(e));
+    if (int rc = launch_check("chain_rollout_kernel")) return rc;
     if (flags & MPPI_FLAG_FUSED_UPDATE) c->cur ^= 1;
     c->x_flipped = (flags & MPPI_FLAG_FUSED_UPDATE) && (flags & MPPI_FLAG_EXCHANGE);   // undone on MPPI_E_EXCHANGE
     c->upd_valid = (flags & MPPI_FLAG_FUSED_UPDATE) != 0;
@@ -1777,12 +1684,11 @@ int chain_rollout(mppi_chain_ctx* c, const float* noise_dev, double* S_dev, doub
         // the update's read-back right behind the launch, so what the caller queues next (the next
         // step's noise) does not delay mppi_chain_wait_outputs
         const char* blk = (const char*)(c->d_step + c->cur);
-        if (hipMemcpyAsync(c->h_out, blk + offsetof(ChainStep, u), (size_t)c->cfg.T * kCMax * sizeof(double),
-                           hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipMemcpyAsync(c->h_out + kCMaxVals, blk + offsetof(ChainStep, u_first), (kCMax + 1) * sizeof(double),
-                           hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipEventRecord(c->out_ev, c->stream) != hipSuccess)
-            return fail(MPPI_E_HIP, "update read-back");
+        HIP_TRY(hipMemcpyAsync(c->h_out, blk + offsetof(ChainStep, u), (size_t)c->cfg.T * kCMax * sizeof(double),
+                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_out + kCMaxVals, blk + offsetof(ChainStep, u_first), (kCMax + 1) * sizeof(double),
+                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(c->out_ev, c->stream));
         c->out_posted = true;
     }
     return MPPI_OK;
@@ -1804,50 +1710,13 @@ int mppi_chain_debug_slots(mppi_chain_ctx* c, const float* noise_dev, double* S_
 
 int mppi_chain_exchange_handle(mppi_chain_ctx* c, int world, void* handle_out) {
     if (!c || !handle_out || world < 1 || world > kMaxWorld) return fail(MPPI_E_ARG, "bad argument");
-    if (c->d_inbox && c->xworld_alloc != world) return fail(MPPI_E_ARG, "inbox already sized for another world");
-    const int stride = 2 + c->cfg.T * c->n;
-    if (!c->d_inbox) {
-        const size_t bytes = (size_t)2 * world * (stride + 1) * 16;   // rows and statuses, two parities
-        hipError_t e;
-        if ((e = hipSetDevice(c->device)) != hipSuccess ||
-            (e = hipExtMallocWithFlags(&c->d_inbox, bytes, hipDeviceMallocUncached)) != hipSuccess ||
-            (e = hipMemset(c->d_inbox, 0, bytes)) != hipSuccess ||
-            (e = hipMalloc(&c->d_xrow, stride * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&c->d_xepoch, 256)) != hipSuccess || (e = hipMemset(c->d_xepoch, 0, 256)) != hipSuccess ||
-            (e = hipDeviceSynchronize()) != hipSuccess)
-            return fail(MPPI_E_HIP, std::string("exchange inbox: ") + hipGetErrorString(e));
-        c->xworld_alloc = world;
-        c->xd.bytes = (int)bytes;
-    }
-    const hipError_t e = hipIpcGetMemHandle(static_cast<hipIpcMemHandle_t*>(handle_out), c->d_inbox);
-    if (e != hipSuccess) return fail(MPPI_E_HIP, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e));
-    return MPPI_OK;
+    return c->ex.handle(c->device, 2 + c->cfg.T * c->n, world, handle_out);
 }
 
 int mppi_chain_exchange_attach(mppi_chain_ctx* c, int rank, int world, const void* handles) {
     if (!c || !handles || world < 1 || rank < 0 || rank >= world) return fail(MPPI_E_ARG, "bad argument");
-    if (!c->d_inbox || c->xworld_alloc != world) return fail(MPPI_E_ARG, "call mppi_chain_exchange_handle(world) first");
-    if (c->xd.world) return fail(MPPI_E_ARG, "already attached");
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return fail(MPPI_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    const hipIpcMemHandle_t* h = static_cast<const hipIpcMemHandle_t*>(handles);
-    for (int p = 0; p < world; ++p) {
-        if (p == rank) {
-            c->xd.peer[p] = c->d_inbox;
-            continue;
-        }
-        void* ptr = nullptr;
-        if ((e = hipIpcOpenMemHandle(&ptr, h[p], hipIpcMemLazyEnablePeerAccess)) != hipSuccess)
-            return fail(MPPI_E_HIP, std::string("hipIpcOpenMemHandle: ") + hipGetErrorString(e));
-        c->xopened[p] = ptr;
-        c->xd.peer[p] = ptr;
-    }
-    c->xd.row = c->d_xrow;
-    c->xd.epoch = c->d_xepoch;
-    c->xd.rank = rank;
-    c->xd.world = world;
-    c->xd.timeout_ticks = exchange_timeout_ticks();
-    return MPPI_OK;
+    if (!c->ex.d_inbox || c->ex.world_alloc != world) return fail(MPPI_E_ARG, "call mppi_chain_exchange_handle(world) first");
+    return c->ex.attach(c->device, rank, world, handles);
 }
 
 int mppi_chain_merge_partials(mppi_chain_ctx* c, const double* partials_dev, int nparts, unsigned flags) {
@@ -1861,8 +1730,7 @@ int mppi_chain_merge_partials(mppi_chain_ctx* c, const double* partials_dev, int
                        c->d_weps, nxt, flags)
     MPPI_CHAIN_DISPATCH(c->n, MPPI_M)
 #undef MPPI_M
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MPPI_E_HIP, std::string("chain_merge_kernel: ") + hipGetErrorString(e));
+    if (int rc = launch_check("chain_merge_kernel")) return rc;
     if (flags & MPPI_FLAG_FUSED_UPDATE) c->cur ^= 1;
     c->x_flipped = (flags & MPPI_FLAG_FUSED_UPDATE) && (flags & MPPI_FLAG_EXCHANGE);   // undone on MPPI_E_EXCHANGE
     c->upd_valid = (flags & MPPI_FLAG_FUSED_UPDATE) != 0;
@@ -1873,9 +1741,8 @@ int mppi_chain_merge_partials(mppi_chain_ctx* c, const double* partials_dev, int
 int mppi_chain_get_weighted_noise(mppi_chain_ctx* c, double* w_eps_host) {
     if (!c || !w_eps_host) return fail(MPPI_E_ARG, "null argument");
     const size_t bytes = (size_t)c->cfg.T * c->n * sizeof(double);
-    if (hipMemcpyAsync(c->h_buf, c->d_weps, bytes + sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-        return fail(MPPI_E_HIP, "weighted noise read-back");
+    HIP_TRY(hipMemcpyAsync(c->h_buf, c->d_weps, bytes + sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     memcpy(w_eps_host, c->h_buf, bytes);
     c->last_eta = c->h_buf[(size_t)c->cfg.T * c->n];
     return check_tmo(c);
@@ -1884,10 +1751,9 @@ int mppi_chain_get_weighted_noise(mppi_chain_ctx* c, double* w_eps_host) {
 int mppi_chain_get_nominal(mppi_chain_ctx* c, double* u_host) {
     if (!c || !u_host) return fail(MPPI_E_ARG, "null argument");
     const int n = c->n, T = c->cfg.T;
-    if (hipMemcpyAsync(c->h_buf, (const char*)(c->d_step + c->cur) + offsetof(ChainStep, u),
-                       (size_t)T * kCMax * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-        return fail(MPPI_E_HIP, "nominal read-back");
+    HIP_TRY(hipMemcpyAsync(c->h_buf, (const char*)(c->d_step + c->cur) + offsetof(ChainStep, u),
+                           (size_t)T * kCMax * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     for (int t = 0; t < T; ++t)
         for (int d = 0; d < n; ++d) u_host[t * n + d] = c->h_buf[t * kCMax + d];
     return check_tmo(c);
@@ -1947,15 +1813,14 @@ int mppi_chain_wait_outputs(mppi_chain_ctx* c, const double* x0, double* u_out, 
     const int n = c->n, T = c->cfg.T;
     const double* h = c->h_out;
     if (c->out_posted) {   // MPPI_FLAG_HOST_OUT: the copy is already queued behind the launch
-        if (hipEventSynchronize(c->out_ev) != hipSuccess) return fail(MPPI_E_HIP, "update read-back");
+        HIP_TRY(hipEventSynchronize(c->out_ev));
     } else {
         const char* blk = (const char*)(c->d_step + c->cur);
-        if (hipMemcpyAsync(c->h_out, blk + offsetof(ChainStep, u), (size_t)T * kCMax * sizeof(double),
-                           hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipMemcpyAsync(c->h_out + kCMaxVals, blk + offsetof(ChainStep, u_first), (kCMax + 1) * sizeof(double),
-                           hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess)
-            return fail(MPPI_E_HIP, "update read-back");
+        HIP_TRY(hipMemcpyAsync(c->h_out, blk + offsetof(ChainStep, u), (size_t)T * kCMax * sizeof(double),
+                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_out + kCMaxVals, blk + offsetof(ChainStep, u_first), (kCMax + 1) * sizeof(double),
+                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (int rc = check_tmo(c)) return rc;
     c->last_eta = h[kCMaxVals + kCMax];
@@ -1987,18 +1852,14 @@ int mppi_chain_rollout_traj(mppi_chain_ctx* c, const double* base_u, const float
     const int n = c->n, T = c->cfg.T;
     const ChainStep* cur = c->d_step + c->cur;
     if (base_u) {
-        if (hipEventSynchronize(c->staged) != hipSuccess) return fail(MPPI_E_HIP, "staging event");
+        HIP_TRY(hipEventSynchronize(c->staged));
         for (int i = 0; i < T * n; ++i) c->h_base[i] = (float)base_u[i];
-        if (hipMemcpyAsync(c->d_base, c->h_base, (size_t)T * n * sizeof(float), hipMemcpyHostToDevice, c->stream) !=
-                hipSuccess ||
-            hipEventRecord(c->staged, c->stream) != hipSuccess)
-            return fail(MPPI_E_HIP, "base upload");
+        HIP_TRY(hipMemcpyAsync(c->d_base, c->h_base, (size_t)T * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->staged, c->stream));
     } else {
         // the nominal u of the current step block: ua[t][0:n], row stride 2 kCMax floats
-        if (hipMemcpy2DAsync(c->d_base, n * sizeof(float), (const char*)cur + offsetof(ChainStep, ua),
-                             2 * kCMax * sizeof(float), n * sizeof(float), T, hipMemcpyDeviceToDevice,
-                             c->stream) != hipSuccess)
-            return fail(MPPI_E_HIP, "base copy");
+        HIP_TRY(hipMemcpy2DAsync(c->d_base, n * sizeof(float), (const char*)cur + offsetof(ChainStep, ua),
+                                 2 * kCMax * sizeof(float), n * sizeof(float), T, hipMemcpyDeviceToDevice, c->stream));
     }
     const int blocks = (K + kCT - 1) / kCT;
 #define MPPI_T(N)                                                                                                \
@@ -2012,9 +1873,7 @@ int mppi_chain_rollout_traj(mppi_chain_ctx* c, const double* base_u, const float
     } while (0)
     MPPI_CHAIN_DISPATCH(n, MPPI_T)
 #undef MPPI_T
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MPPI_E_HIP, std::string("chain_traj_kernel: ") + hipGetErrorString(e));
-    return MPPI_OK;
+    return launch_check("chain_traj_kernel");
 }
 
 int mppi_chain_noise_philox(mppi_chain_ctx* c, unsigned long long seed, unsigned long long step, float* out_dev) {
@@ -2025,14 +1884,12 @@ int mppi_chain_noise_philox(mppi_chain_ctx* c, unsigned long long seed, unsigned
                        (long long)c->cfg.k_offset, seed, step, c->chol, out_dev)
     MPPI_CHAIN_DISPATCH(c->n, MPPI_PH);
 #undef MPPI_PH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MPPI_E_HIP, std::string("chain_philox_kernel: ") + hipGetErrorString(e));
-    return MPPI_OK;
+    return launch_check("chain_philox_kernel");
 }
 
 int mppi_chain_sync(mppi_chain_ctx* c) {
     if (!c) return fail(MPPI_E_ARG, "null context");
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(MPPI_E_HIP, "stream synchronize");
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return check_tmo(c);
 }
 

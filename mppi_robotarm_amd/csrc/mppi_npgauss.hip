@@ -527,12 +527,6 @@ struct mppi_np_ctx {
 
 namespace {
 
-#define NP_CHECK(expr)                                                                    \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return fail(MPPI_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct Plan {
     long long need, pairs, A, nblk;
     int P, streams;
@@ -576,7 +570,7 @@ extern "C" {
 int mppi_np_ctx_create(int device, const double* log_params, mppi_np_ctx** out) {
     if (!out || !log_params) return fail(MPPI_E_ARG, "null argument");
     *out = nullptr;
-    NP_CHECK(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     mppi_np_ctx* c = new mppi_np_ctx();
     c->device = device;
     hipError_t e;
@@ -625,8 +619,8 @@ int mppi_np_set_jumps(mppi_np_ctx* c, int block_stride, int streams, const unsig
     if (!c || (streams > 1 && !polys)) return fail(MPPI_E_ARG, "null argument");
     if (words != kPolyWords || block_stride < 1 || streams < 1 || streams > MPPI_NP_MAX_STREAMS)
         return fail(MPPI_E_ARG, "mppi_np_set_jumps: bad stride, stream count or polynomial size");
-    NP_CHECK(hipSetDevice(c->device));
-    if (c->pending) NP_CHECK(hipEventSynchronize(c->done));   // the buffers may be in use by the last draw
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->pending) HIP_TRY(hipEventSynchronize(c->done));   // the buffers may be in use by the last draw
     (void)hipFree(c->d_nibs);
     (void)hipFree(c->d_jumped);
     c->d_nibs = nullptr;
@@ -652,9 +646,9 @@ int mppi_np_set_jumps(mppi_np_ctx* c, int block_stride, int streams, const unsig
                         nibs[((size_t)ch * G + j / kNibS) * kNibS + j % kNibS] = v;
                 }
             }
-        NP_CHECK(hipMalloc(&c->d_nibs, nibs.size() * sizeof(uint32_t)));
-        NP_CHECK(hipMemcpy(c->d_nibs, nibs.data(), nibs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        NP_CHECK(hipMalloc(&c->d_jumped, (size_t)ns * R * kN * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&c->d_nibs, nibs.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(c->d_nibs, nibs.data(), nibs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&c->d_jumped, (size_t)ns * R * kN * sizeof(uint32_t)));
         c->jG = G;
         c->jR = R;
         c->jcpw = cpw;
@@ -678,9 +672,9 @@ int mppi_np_draw(mppi_np_ctx* c, void* stream, const mppi_np_state* st, long lon
     const Plan p = make_plan(n, st->pos, st->has_gauss);
     if (p.P != c->poly_P || p.streams > c->poly_streams)
         return fail(MPPI_E_ARG, "mppi_np_draw: the jump polynomials of mppi_np_plan's stride and count are not set");
-    NP_CHECK(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (c->pending) NP_CHECK(hipEventSynchronize(c->done));
+    if (c->pending) HIP_TRY(hipEventSynchronize(c->done));
     // A draw that starts where the last one ended (the drop-ins' queued next-call draw does) finds its first 34
     // blocks in the last draw's words already (generated with ~1600 blocks of slack at c3): the jumps read that
     // slice and the sequence is not twisted again.
@@ -696,7 +690,7 @@ int mppi_np_draw(mppi_np_ctx* c, void* stream, const mppi_np_state* st, long lon
         (void)hipFree(c->d_words);
         c->d_words = nullptr;
         c->words_cap = 0;
-        NP_CHECK(hipMalloc(&c->d_words, words * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&c->d_words, words * sizeof(uint32_t)));
         c->words_cap = words;
     }
     const long long nwg = (p.A + kAttPerWG - 1) / kAttPerWG;
@@ -704,13 +698,13 @@ int mppi_np_draw(mppi_np_ctx* c, void* stream, const mppi_np_state* st, long lon
         (void)hipFree(c->d_look);
         c->d_look = nullptr;
         c->look_cap = 0;
-        NP_CHECK(hipMalloc(&c->d_look, nwg * sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc(&c->d_look, nwg * sizeof(unsigned long long)));
         c->look_cap = (size_t)nwg;
         c->epoch = 0;   // cleared below
     }
     if (++c->epoch >= (1ull << (64 - kLookShift - 2)) || c->epoch == 1) {
         c->epoch = 1;
-        NP_CHECK(hipMemsetAsync(c->d_look, 0, c->look_cap * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(c->d_look, 0, c->look_cap * sizeof(unsigned long long), s));
     }
     memcpy(c->h_key, st->key, kN * sizeof(uint32_t));   // read by the kernels over the link (no copy)
     if (p.streams > 1) {
@@ -748,7 +742,7 @@ int mppi_np_draw(mppi_np_ctx* c, void* stream, const mppi_np_state* st, long lon
     // the event marks the end of whatever was queued, even after a failed launch: the next draw waits for it
     // before it rewrites the host-mapped key the queued kernels read
     const hipError_t le = hipGetLastError();
-    NP_CHECK(hipEventRecord(c->done, s));
+    HIP_TRY(hipEventRecord(c->done, s));
     c->pending = true;
     if (le != hipSuccess) return fail(MPPI_E_HIP, std::string("mppi_np_draw: ") + hipGetErrorString(le));
     c->last_nblk = p.nblk;
@@ -759,7 +753,7 @@ int mppi_np_draw_result(mppi_np_ctx* c, mppi_np_state* st_out) {
     if (!c || !st_out) return fail(MPPI_E_ARG, "null argument");
     if (!c->pending) return fail(MPPI_E_ARG, "mppi_np_draw_result: no draw pending");
     c->pending = false;
-    NP_CHECK(hipEventSynchronize(c->done));
+    HIP_TRY(hipEventSynchronize(c->done));
     if (c->h_out->status != 0)
         return fail(MPPI_E_RETRY, "mppi_np_draw: fewer accepted attempts than pairs wanted, or the look-back gave up (output incomplete)");
     *st_out = c->h_out->st;

@@ -777,13 +777,7 @@ struct mppi_ctx {
     double* d_dout = nullptr;       // its device view
     unsigned dseq = 0;
     double dropin_us[6] = {};       // phase ends of the last mppi_step_dropin (mppi_debug_dropin_times)
-    double* d_slab = nullptr;
-    double* d_gslab = nullptr;
-    unsigned* d_counter = nullptr;  // [ngroups + 1] arrival counters (counter hand-off), then the epoch word
-    unsigned* d_epoch = nullptr;    // granule epoch (poll hand-off), inside the d_counter block
-    bool poll = false;              // granule hand-off (grid <= one workgroup per CU)
-    unsigned* h_tmo = nullptr;      // host-mapped: a bounded in-launch spin gave up
-    unsigned* d_tmo = nullptr;
+    mppi_host::Handoff hand;        // hand-off form, its buffers and the time-out words
     double* d_weps = nullptr;
     double* h_buf = nullptr;    // pinned D2H staging, 2 * kMaxT doubles
     float2* d_base = nullptr;   // traj base controls
@@ -799,47 +793,12 @@ struct mppi_ctx {
     std::chrono::steady_clock::time_point step_t0{};   // start of the current drop-in step (phase times)
     double sig_inv[4];
     unsigned long long* d_dbg = nullptr;  // diagnostic stamp buffer (MPPI_STAMPS builds)
-    // node-level exchange (mppi_exchange_*): inbox, this rank's row, epoch, peer mappings
-    XDesc xd{};
-    void* d_inbox = nullptr;
-    double* d_xrow = nullptr;
-    unsigned* d_xepoch = nullptr;
-    int xworld_alloc = 0;
-    void* xopened[kMaxWorld] = {};
+    mppi_host::Exchange ex;         // node-level exchange (mppi_exchange_*)
 };
 
-namespace mppi_host {
 namespace {
-thread_local std::string g_err;
-}
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-const char* last_error() { return g_err.c_str(); }
-unsigned exchange_timeout_ticks() {
-    const char* e = getenv("MPPI_EXCHANGE_TIMEOUT_US");
-    const long v = e ? strtol(e, nullptr, 10) : 0;
-    return v > 0 && v < 40000000 ? (unsigned)(v * 100) : 0u;   // s_memrealtime runs at 100 MHz
-}
-}  // namespace mppi_host
-
-namespace {
-using mppi_host::exchange_timeout_ticks;
 using mppi_host::fail;
-
-#define HIP_TRY(expr)                                                                 \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess)                                                         \
-            return fail(MPPI_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-int launch_check(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MPPI_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return MPPI_OK;
-}
+using mppi_host::launch_check;
 
 template <int L, int N>
 int occupancy(int* per_cu) {
@@ -847,24 +806,16 @@ int occupancy(int* per_cu) {
 }
 
 int check_timeout(mppi_ctx* c) {
-    // tmo[0]: a local hand-off gave up (kTmoLocal); tmo[1]: the exchange's verdict bits (mppi_device.h)
-    const unsigned v = c->h_tmo ? __atomic_load_n(c->h_tmo, __ATOMIC_ACQUIRE) | __atomic_load_n(c->h_tmo + 1, __ATOMIC_ACQUIRE)
-                                : 0u;
-    if (!v) return MPPI_OK;
-    c->h_tmo[0] = c->h_tmo[1] = 0;
+    unsigned v;
+    const int rc = c->hand.take_timeout(&v);
     if (v == kTmoExchange) {
         // every rank of the step reports it and none applied the update: back to the nominal before the launch
         if (c->x_flipped) c->cur ^= 1;
         c->x_flipped = false;
         c->upd_valid = false;
         c->nominal_published = false;
-        return fail(MPPI_E_EXCHANGE, "multi-GPU exchange: a rank's row did not arrive within the bound on every "
-                                     "rank of this step; no rank applied the update (run the step again)");
     }
-    if (v & kTmoSplit)
-        return fail(MPPI_E_HIP, "multi-GPU exchange: this rank had every row but not every rank's verdict within "
-                                "the bound; other ranks may have applied the step, so it cannot be re-run");
-    return fail(MPPI_E_HIP, "in-launch hand-off timed out (workgroups not co-resident?); results invalid");
+    return rc;
 }
 
 int auto_lps(int K_local) {
@@ -887,6 +838,46 @@ int auto_lps(int K_local) {
     if (waves1 >= 64) return 8;
     return 16;
 }
+
+// The device side of mppi_ctx_create: the hand-off form from the rollout kernel's occupancy, then every
+// buffer (on an error the caller destroys the half-built context).
+int alloc(mppi_ctx* c) {
+    HIP_TRY(hipSetDevice(c->device));
+    int ncu = 0, per_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+    {
+        const int lps = c->lps;
+        int rc = 0;
+        if (c->nt == 512)
+            rc = lps == 1 ? occupancy<1, 512>(&per_cu) : lps == 2 ? occupancy<2, 512>(&per_cu)
+               : lps == 4 ? occupancy<4, 512>(&per_cu) : lps == 8 ? occupancy<8, 512>(&per_cu)
+               : occupancy<16, 512>(&per_cu);
+        else
+            rc = lps == 1 ? occupancy<1, 256>(&per_cu) : lps == 2 ? occupancy<2, 256>(&per_cu)
+               : lps == 4 ? occupancy<4, 256>(&per_cu) : lps == 8 ? occupancy<8, 256>(&per_cu)
+               : occupancy<16, 256>(&per_cu);
+        if (rc != 0) per_cu = 0;
+    }
+    if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + 2 * c->cfg.T, 0)) return rc;
+    c->kc.acquire = c->hand.acquire;
+    HIP_TRY(hipMalloc(&c->d_step, 2 * sizeof(DevStep)));
+    HIP_TRY(hipMalloc(&c->d_weps, 2 * kMaxT * sizeof(double)));
+    HIP_TRY(hipMalloc(&c->d_base, kMaxT * sizeof(float2)));
+    HIP_TRY(hipMalloc(&c->d_upd, kMaxT * sizeof(float2)));
+    HIP_TRY(hipHostMalloc(&c->h_out, 2 * kMaxT * sizeof(double) + 4 * kMaxT * sizeof(float), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&c->h_step, sizeof(DevStep), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&c->h_buf, 2 * kMaxT * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&c->h_base, kMaxT * sizeof(float2), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&c->h_dout, (4 + 2 * kMaxT) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer((void**)&c->d_dout, c->h_dout, 0));
+    HIP_TRY(hipEventCreateWithFlags(&c->staged, hipEventDisableTiming));
+    HIP_TRY(hipMemset(c->d_step, 0, 2 * sizeof(DevStep)));
+    HIP_TRY(hipMemset(c->d_weps, 0, 2 * kMaxT * sizeof(double)));
+    HIP_TRY(hipDeviceSynchronize());
+    memset(c->h_step, 0, sizeof(DevStep));
+    memset(c->h_dout, 0, (4 + 2 * kMaxT) * sizeof(double));
+    return MPPI_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -904,9 +895,7 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
     if (!cfg || !out) return fail(MPPI_E_ARG, "null argument");
     *out = nullptr;
     if (cfg->T < 1 || cfg->T > MPPI_MAX_T) return fail(MPPI_E_ARG, "T must be in [1, 128]");
-    if (cfg->K_local < 1 || cfg->K_total < cfg->K_local || cfg->k_offset < 0 ||
-        cfg->k_offset + (long long)cfg->K_local > cfg->K_total)
-        return fail(MPPI_E_ARG, "bad sample geometry (K_local, K_total, k_offset)");
+    if (int rc = mppi_host::check_sample_geometry(cfg->K_local, cfg->K_total, cfg->k_offset)) return rc;
     const double* S = cfg->sigma;
     const double det = S[0] * S[3] - S[1] * S[2];
     if (det == 0.0 || !isfinite(det)) return fail(MPPI_E_SINGULAR, "Singular matrix");
@@ -939,16 +928,7 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
     const mppi_arm_params& a = cfg->arm;
     KConst& k = c->kc;
     memset(&k, 0, sizeof(k));
-    k.K_local = cfg->K_local;
-    k.T = cfg->T;
-    k.k_offset = cfg->k_offset;
-    {
-        const double thr = (1.0 - cfg->param_exploration) * (double)cfg->K_total;  // control.py:98
-        long long kx = thr <= 0.0 ? 0 : (long long)ceil(thr);
-        if (kx > cfg->K_total) kx = cfg->K_total;
-        k.k_exploit = (int)kx;
-    }
-    k.nblocks = c->nblocks;
+    mppi_host::set_common_consts(k, *cfg, c->nblocks);
     k.dt = (float)cfg->delta_t;
     k.fk1 = (float)a.fk_l1;
     k.fk2 = (float)a.fk_l2;
@@ -962,76 +942,12 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
         k.sw[i] = (float)(cfg->stage_cost_weight[i] * 10000.0);     // control.py:185
         k.tw[i] = (float)(cfg->terminal_cost_weight[i] * 10000.0);  // control.py:198
     }
-    k.lambda = cfg->param_lambda;
-    k.inv_lambda = 1.0 / cfg->param_lambda;
-    // control.py:45 fixes gamma at construction; the caller passes it as given
-    k.gamma = isnan(cfg->param_gamma) ? cfg->param_lambda * (1.0 - cfg->param_alpha) : cfg->param_gamma;
     for (int i = 0; i < 4; ++i) k.sig_inv[i] = c->sig_inv[i];
 
-    auto cleanup_fail = [&](int rc) {
+    if (int rc = alloc(c)) {
         mppi_ctx_destroy(c);
         return rc;
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess) return cleanup_fail(fail(MPPI_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)));
-    // hand-off form: tagged-granule polling when every workgroup is resident at
-    // once (at most one per CU, the measured form); arrival counters otherwise,
-    // with an agent acquire once workgroups share CUs.  MPPI_HANDOFF=counter
-    // forces the counter form (tests).
-    int ncu = 0, per_cu = 0;
-    if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess)
-        return cleanup_fail(fail(MPPI_E_HIP, std::string("device attributes: ") + hipGetErrorString(e)));
-    {
-        int rc = 0;
-        if (c->nt == 512)
-            rc = lps == 1 ? occupancy<1, 512>(&per_cu) : lps == 2 ? occupancy<2, 512>(&per_cu)
-               : lps == 4 ? occupancy<4, 512>(&per_cu) : lps == 8 ? occupancy<8, 512>(&per_cu)
-               : occupancy<16, 512>(&per_cu);
-        else
-            rc = lps == 1 ? occupancy<1, 256>(&per_cu) : lps == 2 ? occupancy<2, 256>(&per_cu)
-               : lps == 4 ? occupancy<4, 256>(&per_cu) : lps == 8 ? occupancy<8, 256>(&per_cu)
-               : occupancy<16, 256>(&per_cu);
-        if (rc != 0) per_cu = 0;
     }
-    c->poll = per_cu >= 1 && c->nblocks <= ncu;
-    if (const char* ev = getenv("MPPI_HANDOFF")) {
-        if (!strcmp(ev, "counter")) c->poll = false;
-    }
-    k.acquire = (!c->poll && c->nblocks > ncu) ? 1 : 0;
-    const size_t val = c->poll ? 16 : sizeof(double);  // granule or plain fp64
-    const size_t slab = (size_t)c->nblocks * (2 + 2 * cfg->T) * val;
-    const int ngroups = (c->nblocks + kGroup - 1) / kGroup;
-    const size_t gslab = (size_t)ngroups * (2 + 2 * cfg->T) * val;
-    const size_t ctr_bytes = ((size_t)(ngroups + 2) * sizeof(unsigned) + 255) & ~(size_t)255;
-    if ((e = hipMalloc(&c->d_step, 2 * sizeof(DevStep))) != hipSuccess ||
-        (e = hipMalloc(&c->d_slab, slab)) != hipSuccess ||
-        (e = hipMalloc(&c->d_gslab, gslab)) != hipSuccess ||
-        (e = hipMalloc(&c->d_counter, ctr_bytes)) != hipSuccess ||
-        (e = hipMalloc(&c->d_weps, 2 * kMaxT * sizeof(double))) != hipSuccess ||
-        (e = hipMalloc(&c->d_base, kMaxT * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc(&c->d_upd, kMaxT * sizeof(float2))) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_out, 2 * kMaxT * sizeof(double) + 4 * kMaxT * sizeof(float), hipHostMallocDefault)) !=
-            hipSuccess ||
-        (e = hipHostMalloc(&c->h_step, sizeof(DevStep), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_buf, 2 * kMaxT * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_base, kMaxT * sizeof(float2), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_tmo, 256, hipHostMallocMapped)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_dout, (4 + 2 * kMaxT) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent)) !=
-            hipSuccess ||
-        (e = hipHostGetDevicePointer((void**)&c->d_dout, c->h_dout, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void**)&c->d_tmo, c->h_tmo, 0)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->staged, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipMemset(c->d_counter, 0, ctr_bytes)) != hipSuccess ||
-        (e = hipMemset(c->d_slab, 0, slab)) != hipSuccess ||
-        (e = hipMemset(c->d_gslab, 0, gslab)) != hipSuccess ||
-        (e = hipMemset(c->d_step, 0, 2 * sizeof(DevStep))) != hipSuccess ||
-        (e = hipMemset(c->d_weps, 0, 2 * kMaxT * sizeof(double))) != hipSuccess ||
-        (e = hipDeviceSynchronize()) != hipSuccess)
-        return cleanup_fail(fail(MPPI_E_HIP, std::string("allocation: ") + hipGetErrorString(e)));
-    memset(c->h_step, 0, sizeof(DevStep));
-    memset(c->h_dout, 0, (4 + 2 * kMaxT) * sizeof(double));
-    c->h_tmo[0] = c->h_tmo[1] = 0;
-    c->d_epoch = c->d_counter + ngroups + 1;
     *out = c;
     return MPPI_OK;
 }
@@ -1041,22 +957,15 @@ void mppi_ctx_destroy(mppi_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipDeviceSynchronize();
     (void)hipFree(c->d_step);
-    (void)hipFree(c->d_slab);
-    (void)hipFree(c->d_counter);
-    (void)hipFree(c->d_gslab);
+    c->hand.release();
     (void)hipFree(c->d_weps);
     (void)hipFree(c->d_base);
     (void)hipFree(c->d_upd);
     if (c->h_out) (void)hipHostFree(c->h_out);
-    for (void* p : c->xopened)
-        if (p) (void)hipIpcCloseMemHandle(p);
-    (void)hipFree(c->d_inbox);
-    (void)hipFree(c->d_xrow);
-    (void)hipFree(c->d_xepoch);
+    c->ex.release();
     if (c->h_step) (void)hipHostFree(c->h_step);
     if (c->h_buf) (void)hipHostFree(c->h_buf);
     if (c->h_base) (void)hipHostFree(c->h_base);
-    if (c->h_tmo) (void)hipHostFree(c->h_tmo);
     if (c->h_dout) (void)hipHostFree(c->h_dout);
     if (c->staged) (void)hipEventDestroy(c->staged);
     delete c;
@@ -1090,26 +999,8 @@ int stage_inputs(mppi_ctx* c, const double* x0, const double* window, int W, con
     if (!x0 || !window) return fail(MPPI_E_ARG, "null argument");
     if (W < 1 || W > MPPI_SEARCH_LEN) return fail(MPPI_E_ARG, "window rows must be in [1, 30]");
     StepStatic& h = c->stat;
-    double cx = 0.0, cy = 0.0;
-    for (int j = 0; j < W; ++j) {
-        cx += window[4 * j];
-        cy += window[4 * j + 1];
-    }
-    cx /= W;
-    cy /= W;
-    for (int j = 0; j < kSlots; ++j) {
-        if (j < W) {
-            const double* r = window + 4 * j;
-            h.win[j] = make_float4((float)r[0], (float)r[1], (float)r[2], (float)r[3]);
-            const double rx = r[0] - cx, ry = r[1] - cy;
-            h.key[j] = make_float4((float)(-2.0 * rx), (float)(-2.0 * ry), (float)(rx * rx + ry * ry), 0.f);
-        } else {
-            h.win[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            h.key[j] = make_float4(0.f, 0.f, kPadKey, 0.f);
-        }
-    }
+    mppi_host::stage_window(window, W, h.win, h.key, &h.ctr);
     h.x0 = make_float4((float)x0[0], (float)x0[1], (float)x0[2], (float)x0[3]);
-    h.ctr = make_float4((float)cx, (float)cy, (float)W, 0.f);
     if (!u) return MPPI_OK;
     const int T = c->cfg.T;
     if (skip_same && c->nominal_published && !memcmp(u, c->h_dout + 4, 2 * (size_t)T * sizeof(double)))
@@ -1221,20 +1112,20 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
     if ((flags & MPPI_FLAG_FUSED_UPDATE) && c->cfg.T < 5)
         return fail(MPPI_E_ARG, "device median filter needs T >= 5 (use the host update)");
     if (flags & MPPI_FLAG_EXCHANGE) {
-        if (c->xd.world < 1) return fail(MPPI_E_ARG, "MPPI_FLAG_EXCHANGE before mppi_exchange_attach");
+        if (c->ex.xd.world < 1) return fail(MPPI_E_ARG, "MPPI_FLAG_EXCHANGE before mppi_exchange_attach");
         if (partial_dev) return fail(MPPI_E_ARG, "MPPI_FLAG_EXCHANGE merges on device: no partial_out");
-        partial_dev = c->d_xrow;
+        partial_dev = c->ex.d_xrow;
     }
     const DevStep* cur = c->d_step + c->cur;
     DevStep* nxt = c->d_step + (c->cur ^ 1);
     const float2* nz = reinterpret_cast<const float2*>(noise_dev);
 #define MPPI_LAUNCH(L, NTH, P)                                                                                   \
     hipLaunchKernelGGL((rollout_kernel<L, NTH, P>), dim3(c->nblocks), dim3(NTH), 0, c->stream, c->kc, c->stat, cur, nz, \
-                       S_dev, c->d_slab, c->d_gslab, c->d_counter, partial_dev, c->d_weps, nxt, flags, c->xd,          \
-                       c->d_epoch, c->d_tmo, reinterpret_cast<float*>(c->d_upd), ho, c->d_dbg)
+                       S_dev, c->hand.d_slab, c->hand.d_gslab, c->hand.d_counter, partial_dev, c->d_weps, nxt, flags,  \
+                       c->ex.xd, c->hand.d_epoch, c->hand.d_tmo, reinterpret_cast<float*>(c->d_upd), ho, c->d_dbg)
 #define MPPI_LAUNCH_P(L, NTH)                \
     do {                                     \
-        if (c->poll) MPPI_LAUNCH(L, NTH, true);  \
+        if (c->hand.poll) MPPI_LAUNCH(L, NTH, true);  \
         else MPPI_LAUNCH(L, NTH, false);     \
     } while (0)
     if (c->nt == 512) {
@@ -1267,46 +1158,13 @@ extern "C" {
 
 int mppi_exchange_handle(mppi_ctx* c, int world, void* handle_out) {
     if (!c || !handle_out || world < 1 || world > kMaxWorld) return fail(MPPI_E_ARG, "bad argument");
-    if (c->d_inbox && c->xworld_alloc != world) return fail(MPPI_E_ARG, "inbox already sized for another world");
-    const int stride = 2 + 2 * c->cfg.T;
-    if (!c->d_inbox) {
-        const size_t bytes = (size_t)2 * world * (stride + 1) * 16;   // rows and statuses, two parities
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipExtMallocWithFlags(&c->d_inbox, bytes, hipDeviceMallocUncached));
-        HIP_TRY(hipMemset(c->d_inbox, 0, bytes));
-        HIP_TRY(hipMalloc(&c->d_xrow, stride * sizeof(double)));
-        HIP_TRY(hipMalloc(&c->d_xepoch, 256));
-        HIP_TRY(hipMemset(c->d_xepoch, 0, 256));
-        HIP_TRY(hipDeviceSynchronize());
-        c->xworld_alloc = world;
-        c->xd.bytes = (int)bytes;
-    }
-    HIP_TRY(hipIpcGetMemHandle(static_cast<hipIpcMemHandle_t*>(handle_out), c->d_inbox));
-    return MPPI_OK;
+    return c->ex.handle(c->device, 2 + 2 * c->cfg.T, world, handle_out);
 }
 
 int mppi_exchange_attach(mppi_ctx* c, int rank, int world, const void* handles) {
     if (!c || !handles || world < 1 || rank < 0 || rank >= world) return fail(MPPI_E_ARG, "bad argument");
-    if (!c->d_inbox || c->xworld_alloc != world) return fail(MPPI_E_ARG, "call mppi_exchange_handle(world) first");
-    if (c->xd.world) return fail(MPPI_E_ARG, "already attached");
-    HIP_TRY(hipSetDevice(c->device));
-    const hipIpcMemHandle_t* h = static_cast<const hipIpcMemHandle_t*>(handles);
-    for (int p = 0; p < world; ++p) {
-        if (p == rank) {
-            c->xd.peer[p] = c->d_inbox;
-            continue;
-        }
-        void* ptr = nullptr;
-        HIP_TRY(hipIpcOpenMemHandle(&ptr, h[p], hipIpcMemLazyEnablePeerAccess));
-        c->xopened[p] = ptr;
-        c->xd.peer[p] = ptr;
-    }
-    c->xd.row = c->d_xrow;
-    c->xd.epoch = c->d_xepoch;
-    c->xd.rank = rank;
-    c->xd.world = world;
-    c->xd.timeout_ticks = exchange_timeout_ticks();
-    return MPPI_OK;
+    if (!c->ex.d_inbox || c->ex.world_alloc != world) return fail(MPPI_E_ARG, "call mppi_exchange_handle(world) first");
+    return c->ex.attach(c->device, rank, world, handles);
 }
 
 int mppi_merge_partials(mppi_ctx* c, const double* partials_dev, int n, unsigned flags) {
@@ -1447,7 +1305,7 @@ int dropin_launch(mppi_ctx* c, const double* x0, const double* window, int W, co
     if (int rc = stage_inputs(c, x0, window, W, u, true)) return rc;
     mark(0);
     // with an exchange attached the launch also trades rows with the other ranks
-    const unsigned fl = MPPI_FLAG_FUSED_UPDATE | MPPI_FLAG_HOST_OUT | (c->xd.world >= 1 ? MPPI_FLAG_EXCHANGE : 0u);
+    const unsigned fl = MPPI_FLAG_FUSED_UPDATE | MPPI_FLAG_HOST_OUT | (c->ex.xd.world >= 1 ? MPPI_FLAG_EXCHANGE : 0u);
     if (int rc = launch_rollout(c, noise_dev, S_dev, nullptr, fl, next_host_out(c, fl))) return rc;
     mark(1);
     // the next step's noise, queued behind this step's rollout (stream order: the
@@ -1595,7 +1453,7 @@ int mppi_sync(mppi_ctx* c) {
 
 int mppi_ctx_handoff(const mppi_ctx* c, int* poll) {
     if (!c || !poll) return fail(MPPI_E_ARG, "null argument");
-    *poll = c->poll ? 1 : 0;
+    *poll = c->hand.poll ? 1 : 0;
     return MPPI_OK;
 }
 
