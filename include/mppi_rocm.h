@@ -80,6 +80,24 @@ typedef struct {
     int lanes_per_sample;      /* 0 = auto; 1, 2, 4, 8 or 16 lanes of a wave per sample */
     double param_gamma;        /* gamma of the control cost (control.py:106), used as   */
                                /* given; NaN: lambda (1 - alpha) as control.py:45       */
+    /* Torque limits: the reference's clamp hook _g (control.py:166-172, shipped with
+     * its two np.clip lines commented out) switched on, clipping its argument in place:
+     *   0  off (the reference as shipped; the value a zeroed config has);
+     *   1  every sampled control v = u[t-1] + eps (or eps alone for an exploration
+     *      sample) is clipped to [u_min, u_max] before _F and before the control-cost
+     *      term gamma u^T Sigma^-1 v (control.py:104-106), in fp32 with the limits
+     *      rounded to nearest; the weights still multiply the unclamped eps
+     *      (control.py:118); the trajectory re-rolls (control.py:133, 143) clip the
+     *      control they feed to _F, the host trajectories in fp64;
+     *   2  also the updated nominal u += w_eps is clipped, in fp64, wherever the update
+     *      runs on the device (MPPI_FLAG_FUSED_UPDATE): what _g(u[t-1]) does in place
+     *      over the loop of control.py:132-134, which runs with visualize_optimal_traj
+     *      only — so mode 2 is the reference with that switch on, mode 1 with it off.
+     * u_min[d] <= u_max[d]; +-inf stands for an absent limit; NaN limits are rejected.
+     * NaN controls are outside the contract (as everywhere else in this library). */
+    int clamp_mode;
+    double u_min[2];
+    double u_max[2];
 } mppi_config;
 
 typedef struct mppi_ctx mppi_ctx;
@@ -88,12 +106,14 @@ typedef struct mppi_ctx mppi_ctx;
  * fields: every field zero except param_gamma = NaN (gamma = lambda (1 - alpha),
  * control.py:45) and arm = sys_params.py:1-13 with the cost's kinematics lengths
  * self.l1 = self.l2 = 1 (control.py:55-56).  A config zeroed with memset or
- * `= {0}` instead has gamma = 0 (no control-cost term).  No device call. */
+ * `= {0}` instead has gamma = 0 (no control-cost term).  clamp_mode stays 0
+ * either way: no torque limits.  No device call. */
 void mppi_config_init(mppi_config *cfg);
 
 /* Context: device scratch (workgroup partial slabs, arrival counter, step
  * parameter block) is allocated here; no call below allocates.  Fails with
- * MPPI_E_SINGULAR for a singular Sigma. */
+ * MPPI_E_SINGULAR for a singular Sigma, and with MPPI_E_ARG for a clamp_mode
+ * outside 0..2 or, with clamp_mode > 0, a NaN limit or u_min[d] > u_max[d]. */
 int mppi_ctx_create(const mppi_config *cfg, int device, void *stream, mppi_ctx **out);
 void mppi_ctx_destroy(mppi_ctx *ctx);
 const char *mppi_last_error(void);

@@ -87,11 +87,13 @@ class ConfigC(C.Structure):
         ("param_exploration", C.c_double), ("sigma", C.c_double * 4),
         ("stage_cost_weight", C.c_double * 4), ("terminal_cost_weight", C.c_double * 4),
         ("arm", ArmParamsC), ("lanes_per_sample", C.c_int), ("param_gamma", C.c_double),
+        # torque limits (_g, control.py:166-172): 0 off, 1 sampled controls, 2 also the updated nominal
+        ("clamp_mode", C.c_int), ("u_min", C.c_double * 2), ("u_max", C.c_double * 2),
     ]
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
-        if "param_gamma" not in kw and len(args) < len(self._fields_):
+        if "param_gamma" not in kw and len(args) <= [f for f, _ in self._fields_].index("param_gamma"):
             self.param_gamma = float("nan")   # gamma = lambda (1 - alpha), control.py:45
 
 

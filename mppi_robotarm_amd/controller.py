@@ -28,7 +28,12 @@ progress prints of control.py:227-229, on by default like the reference),
 ``noise`` ("numpy" = reference RNG stream, or "device" = on-device Philox),
 ``seed`` (device noise), ``lanes_per_sample``, ``arm`` (ArmParams; its
 ``fk_l1``/``fk_l2`` start ``self.l1``/``self.l2``, which the engine follows
-from then on), ``process_group`` (shard the samples over the ranks of a
+from then on), ``u_min`` / ``u_max`` (torque limits, a scalar or one value per
+joint: the reference's clamp hook ``_g``, control.py:166-172, switched on —
+the sampled controls are clipped before the dynamics and the control cost, the
+weights still multiply the unclamped noise, and with ``visualize_optimal_traj``
+the updated nominal is clipped too, exactly as ``_g`` clipping in place would),
+``process_group`` (shard the samples over the ranks of a
 torch.distributed group), ``exchange`` (with a process group: "auto" = the
 in-launch exchange, one launch per rank per step, when its one-step self-check
 against the all-gather passes, else one RCCL all-gather of the per-device
@@ -89,6 +94,8 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
             seed: int = 0,
             lanes_per_sample: int = 0,
             arm: ArmParams | None = None,
+            u_min=None,
+            u_max=None,
             process_group=None,
             exchange: str = "auto",
             host_update: bool = False,
@@ -121,6 +128,8 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
         self.arm = ArmParams(fk_l1=float(self.l1), fk_l2=float(self.l2)) if arm is None else arm
         self._lanes_per_sample = lanes_per_sample
         self.host_update = host_update  # property: forced, or T < 5 (the device median needs T >= 5)
+        self.u_min, self.u_max = u_min, u_max   # properties: torque limits of _g, validated
+        self._limits()                          # u_min <= u_max
         self._bound = None             # what the engine's drop-in tick is bound to (_bind_key)
         self._fast = None              # what the last bound tick checked (calc_control_input's fast test)
 
@@ -134,11 +143,69 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
     def host_update(self, value) -> None:
         self._host_update = bool(value)
 
+    # ------------------------------------------------------------ torque limits (_g, control.py:166-172)
+    @staticmethod
+    def _limit(name: str, value):
+        """A limit as the controller stores it: None, or a read-only fp64 (2,) array (a scalar is broadcast)."""
+        if value is None:
+            return None
+        a = np.asarray(value, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != 2):
+            raise ValueError(f"{name} must be a scalar or have one value per control component (2)")
+        a = np.array(np.broadcast_to(a, (2,)))
+        if np.isnan(a).any():
+            raise ValueError(f"{name} must not be NaN (use +-inf or None for no limit)")
+        a.setflags(write=False)     # rebind to change: the engine key reads the bytes cached at the assignment
+        return a
+
+    @property
+    def u_min(self):
+        """Lower torque limits, fp64 (2,), or None; with u_max the np.clip bounds of _g.  Read on every call like
+        the reference's other attributes: rebinding either rebuilds the engine before the next step."""
+        return self._u_min
+
+    @u_min.setter
+    def u_min(self, value) -> None:
+        self._u_min = self._limit("u_min", value)
+        self._limits_key = None
+
+    @property
+    def u_max(self):
+        """Upper torque limits, fp64 (2,), or None."""
+        return self._u_max
+
+    @u_max.setter
+    def u_max(self, value) -> None:
+        self._u_max = self._limit("u_max", value)
+        self._limits_key = None
+
+    def _limits(self):
+        """(lo, hi) fp64 (2,) with +-inf for an absent side, or None without limits; ValueError if lo > hi."""
+        lo, hi = self._u_min, self._u_max
+        if lo is None and hi is None:
+            return None
+        lo = np.full(2, -np.inf) if lo is None else lo
+        hi = np.full(2, np.inf) if hi is None else hi
+        if (lo > hi).any():
+            raise ValueError(f"u_min {lo.tolist()} exceeds u_max {hi.tolist()}")
+        return lo, hi
+
+    def _clamp_key(self):
+        """What the engine bakes in of the limits: its clamp mode (2: _g also clips the updated nominal, which
+        the reference does in its optimal-trajectory loop, so with visualize_optimal_traj only; control.py:130-133)
+        and the limits' bytes; (0,) without limits."""
+        if self._limits_key is None:
+            lim = self._limits()
+            self._limits_key = () if lim is None else (lim[0].tobytes(), lim[1].tobytes())
+        if not self._limits_key:
+            return (0,)
+        return (2 if self.visualize_optimal_traj else 1,) + self._limits_key
+
     # ------------------------------------------------------------ engine
     def _engine_key(self):
-        """The shared key plus the kinematics lengths self.l1/l2 (control.py:178-179,205-206) and the arm
-        constants."""
-        return super()._engine_key() + (float(self.l1), float(self.l2), self.arm)
+        """The shared key plus the kinematics lengths self.l1/l2 (control.py:178-179,205-206), the arm
+        constants and the torque limits with their mode."""
+        return super()._engine_key() + (float(self.l1), float(self.l2), self.arm, self._clamp_key())
 
     def _get_engine(self, key=None) -> RolloutEngine:
         key = self._engine_key() if key is None else key
@@ -151,11 +218,12 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
             # gamma is fixed at construction in the reference (control.py:45) while lambda is
             # re-read per call: the engine takes gamma as given; the cost's kinematics follow self.l1/l2
             arm = dataclasses.replace(self.arm, fk_l1=float(self.l1), fk_l2=float(self.l2))
+            lo, hi = self._limits() or (None, None)
             self._engine = RolloutEngine(
                 K_local, self.T, self.delta_t, self.param_lambda, self.param_alpha, self.Sigma,
                 self.stage_cost_weight, self.terminal_cost_weight, self.param_exploration, arm,
                 K_total=self.K, k_offset=k_offset, device=device, lanes_per_sample=self._lanes_per_sample,
-                param_gamma=self.param_gamma)
+                param_gamma=self.param_gamma, u_min=lo, u_max=hi, clamp_nominal=bool(self.visualize_optimal_traj))
             self._engine_built_for = key
             self._noise_dev = self._engine.new_noise()
             self._noise_alt = None
@@ -289,6 +357,7 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
 
         optimal_traj = np.zeros((self.T, self.dim_x))
         if self.visualize_optimal_traj:
+            self._g(u)                                     # _g(u[t-1]) for every row, in place (control.py:133)
             optimal_traj = eng.optimal_traj_host(x0, u)
 
         if self.visualze_sampled_trajs:
@@ -359,7 +428,7 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
         return (self.noise_source, self.host_update, self.visualze_sampled_trajs, self.process_group, self.K, self.T,
                 self.param_lambda, self.param_gamma, self.param_exploration, self.delta_t, self.l1, self.l2,
                 self.arm, self.seed, self.keep_costs, self.visualize_optimal_traj, self.verbose,
-                self._noise_ready == (self.seed, self._step_count))
+                self._noise_ready == (self.seed, self._step_count), self._clamp_key())
 
     def _tick_bound(self, observed_x):
         """The bound drop-in tick (engine built, buffers bound, the noise of this step in
@@ -445,7 +514,11 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
 
     # ------------------------------------------------------------ host helpers (reference semantics)
     def _g(self, v: np.ndarray) -> float:
-        """clamp input (disabled in the reference, control.py:166-172)"""
+        """clamp input (control.py:166-172, whose two np.clip lines are commented out): with u_min / u_max
+        set, v (one control, or rows of them) is clipped in place, as those lines would; else the identity"""
+        lim = self._limits()
+        if lim is not None:
+            np.clip(v, lim[0], lim[1], out=v)
         return v
 
     def _get_nearest_waypoint(self, q1: float, q2: float, update_prev_idx: bool = False):

@@ -22,6 +22,11 @@
 //    merges.  One launch covers control.py:81-118.  With MPPI_FLAG_FUSED_UPDATE
 //    the merging workgroup also applies the median filter / update / shift of
 //    control.py:122-149 into the ping-pong step block for the next launch.
+//  * torque limits (mppi_config.clamp_mode; the reference's clamp hook _g, control.py:166-172, switched
+//    on): the CLAMP instantiations of the rollout and trajectory kernels clip every sampled control with one
+//    v_med3_f32 per component before the control cost and the dynamics, and the fused update clips the
+//    nominal in fp64 (mode 2).  The limits travel in ClampK, the kernels' last argument, which the other
+//    instantiations never read: they are the code they were without the feature.
 //  * merge_kernel: the same merge over the all-gathered per-device partials
 //    (multi-GPU), traj_kernel: trajectory re-roll (control.py:129-145),
 //    philox_noise_kernel: counter-based Gaussian noise.
@@ -76,6 +81,16 @@ struct KConst {
     double sig_inv[4];
 };
 
+// Torque limits (mppi_config.clamp_mode, u_min, u_max: _g of control.py:166-172 switched on): the fp64 limits
+// of the nominal's clamp and their nearest fp32 values for the sampled controls'.  The last argument of every
+// kernel that takes it, and read by the CLAMP instantiations only: the others keep their kernel-argument
+// offsets, their registers and their schedule.
+struct ClampK {
+    double u_lo[2], u_hi[2];
+    float v_lo[2], v_hi[2];
+    int mode;
+};
+
 // One semi-implicit Euler step of _F (control.py:234-263) in closed form:
 //   M = [[A + B c2, D + E c2], [D + E c2, D]]   (M22 = m2 lc2^2 + l2 = D)
 //   h = E s2,  G = [P c1 + Q c12, Q c12],  C dq = [-h dq2 (2 dq1 + dq2), h dq1^2]
@@ -108,6 +123,7 @@ struct DynK {
     f32x2 fk;          // (fk1, fk2)
     f32x2 ctr;         // window centre
     f32x2 w01, w23;    // stage weights x 10000
+    f32x2 vlo, vhi;    // torque limits of the sampled controls (CLAMP kernels only; else never set or read)
 };
 
 template <class V>
@@ -141,6 +157,21 @@ __device__ __forceinline__ DynK make_dynk(const KConst& c, float cx, float cy) {
     k.w01 = vgpr_opaque(f32x2{arg_f(c.sw[0]), arg_f(c.sw[1])});
     k.w23 = vgpr_opaque(f32x2{arg_f(c.sw[2]), arg_f(c.sw[3])});
     return k;
+}
+
+// the limits of the sampled controls, beside DynK's other pairs (CLAMP kernels call it, the others never)
+__device__ __forceinline__ void dynk_limits(DynK& k, const ClampK& cl) {
+    k.vlo = vgpr_opaque(f32x2{arg_f(cl.v_lo[0]), arg_f(cl.v_lo[1])});
+    k.vhi = vgpr_opaque(f32x2{arg_f(cl.v_hi[0]), arg_f(cl.v_hi[1])});
+}
+
+// _g with its np.clip lines on (control.py:166-172) for one sampled control: clip(v, lo, hi) per component.
+// gfx950 has no packed fp32 min / max, so either form costs per component; v_med3_f32 is one full-rate VOP3
+// per component where max + min is two, and the median of (v, lo, hi) is the clip exactly because lo <= hi
+// (mppi_ctx_create checks it).  It returns one of its operands unchanged (with +-inf limits, v itself), and
+// unlike fmaxf / fminf the compiler puts no canonicalising v_max in front of it.
+__device__ __forceinline__ f32x2 clamp_v(f32x2 v, const DynK& k) {
+    return f32x2{__builtin_amdgcn_fmed3f(v.x, k.vlo.x, k.vhi.x), __builtin_amdgcn_fmed3f(v.y, k.vlo.y, k.vhi.y)};
 }
 
 __device__ __forceinline__ f32x2 splat(float x) { return f32x2{x, x}; }
@@ -226,23 +257,33 @@ struct HostOut {
     unsigned seq;
 };
 
+// np.clip of one fp64 control (lo <= hi; a NaN passes through, as everywhere outside the contract)
+__host__ __device__ __forceinline__ double clamp_u(double u, double lo, double hi) { return u < lo ? lo : (u > hi ? hi : u); }
+
 // upd (nullable): the updated, not yet shifted controls u_new[t] in fp32, the
 // base of the optimal trajectory (control.py:129-134, mppi_optimal_traj):
 // u_new[t + 1] is this thread's shifted element, u_new[0] one more median.
 // Every thread of the workgroup must call it (it ends with a barrier when
 // host outputs are requested).
-template <int NT>
+// CLAMP: the kernel was built for torque limits; cl.mode == 2 then clips the updated nominal.
+template <int NT, bool CLAMP>
 __device__ void nominal_update_block(DevStep* nxt, const KConst& c, Scratch& sm, double u_src, double u_first,
-                                     float* upd, HostOut ho, bool publish = true) {
+                                     float* upd, HostOut ho, const ClampK& cl, bool publish = true) {
     const int tid = threadIdx.x;
     const int T = c.T;
     if (tid < ((2 * T + 63) & ~63)) {   // whole waves: the DPP pairs stay complete
         const int t = tid >> 1, d = tid & 1;
         const int src = t + 1 < T ? t + 1 : T - 1;
-        const double un = tid < 2 * T ? u_src + median_at(sm, src, d, T, 2) : 0.0;
+        double un = tid < 2 * T ? u_src + median_at(sm, src, d, T, 2) : 0.0;
+        // clamp_mode 2: _g(u[t-1]) over the optimal-trajectory loop clips the whole updated nominal in place
+        // (control.py:132-134), so what is shifted, published and turned into the next launch's a_t is clipped
+        bool clampu = false;
+        if constexpr (CLAMP) clampu = cl.mode == 2;
+        if (clampu) un = clamp_u(un, cl.u_lo[d], cl.u_hi[d]);
         const double other = dpp_f64<0xB1>(un);   // quad_perm [1,0,3,2]: the partner element
         if ((upd || ho.p) && tid < 2) {
-            const double u0 = u_first + median_at(sm, 0, d, T, 2);
+            double u0 = u_first + median_at(sm, 0, d, T, 2);
+            if (clampu) u0 = clamp_u(u0, cl.u_lo[d], cl.u_hi[d]);
             if (upd) upd[d] = (float)u0;
             if (ho.p) ho.p[2 + d] = u0;
         }
@@ -279,13 +320,15 @@ constexpr int kPF = 4;  // noise rows in flight per lane
 // when the grid is at most one workgroup per CU); correctness does not depend
 // on placement or order, every value is tag-checked.  Otherwise (!POLL) the
 // last workgroup to arrive on a counter merges (arrive_last).
-template <int LPS, int NT, bool POLL>
+// CLAMP: the sampled controls are clipped to the torque limits (clamp_mode != 0); the CLAMP = false
+// instantiations carry no trace of it.
+template <int LPS, int NT, bool POLL, bool CLAMP>
 __global__ __launch_bounds__(NT) void rollout_kernel(
     const KConst c, const StepStatic ss, const DevStep* __restrict__ st, const float2* __restrict__ noise,
     double* __restrict__ S_out, double* __restrict__ slab, double* __restrict__ gslab,
     unsigned* __restrict__ counters, double* __restrict__ partial_out, double* __restrict__ w_eps_out,
     DevStep* __restrict__ nxt, unsigned flags, const XDesc xd, unsigned* __restrict__ epoch, unsigned* __restrict__ tmo,
-    float* __restrict__ upd, const HostOut ho, unsigned long long* __restrict__ dbg) {
+    float* __restrict__ upd, const HostOut ho, unsigned long long* __restrict__ dbg, const ClampK cl) {
     __shared__ float4 s_win[kSlots];
     __shared__ float4 s_ua[kMaxT + kPF];   // per-step constants (u_t, a_t); rows >= T repeat row T - 1
     __shared__ double s_redd[NT / 64];
@@ -325,7 +368,8 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     sr.load(ss.key, ss.ctr, tid & (LPS - 1));
     Arm x;
     arm_init(x, ss.x0);
-    const DynK dk = make_dynk(c, sr.cx, sr.cy);
+    DynK dk = make_dynk(c, sr.cx, sr.cy);
+    if constexpr (CLAMP) dynk_limits(dk, cl);
     // the per-step constants go to LDS: the ring reads them there, so no scalar
     // load shares lgkmcnt with the deferred row lookup below
     for (int i = tid; i < T + kPF; i += NT) s_ua[i] = st->ua[i < T ? i : T - 1];
@@ -384,7 +428,9 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
         f32x4 ua = {uring[slot].x, uring[slot].y, uring[slot].z, uring[slot].w};
         asm volatile("" : "+v"(e), "+v"(ua));
         // u[t] + eps (exploit) or eps, control.py:99-101
-        const f32x2 v = __builtin_elementwise_fma(splat(exf), f32x2{ua.x, ua.y}, e);
+        f32x2 v = __builtin_elementwise_fma(splat(exf), f32x2{ua.x, ua.y}, e);
+        // _g in place (control.py:104): the dynamics and the control cost below take the clipped v
+        if constexpr (CLAMP) v = clamp_v(v, dk);
         // (gamma u^T Sigma^-1) v, control.py:106
         S4 = __builtin_elementwise_fma(f32x2{ua.z, ua.w}, v, S4);
         const int tl = t + kPF < T ? t + kPF : T - 1;
@@ -605,21 +651,21 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
         // it lands in the ping-pong block and outputs the host takes only after a good verdict; on a failed
         // exchange the host keeps its block and ignores them (check_timeout), so no rank applies the update
         const unsigned xtag = exchange_send_merge<NT, 1>(xd, geo, c.inv_lambda, sm, w_eps_out, tmo);
-        if (flags & MPPI_FLAG_FUSED_UPDATE) nominal_update_block<NT>(nxt, c, sm, u_cur, u_first, upd, ho, false);
+        if (flags & MPPI_FLAG_FUSED_UPDATE) nominal_update_block<NT, CLAMP>(nxt, c, sm, u_cur, u_first, upd, ho, cl, false);
         exchange_verdict<NT>(xd, geo, xtag, tmo);   // a barrier: every thread's host stores are out
         if ((flags & MPPI_FLAG_FUSED_UPDATE) && ho.p && threadIdx.x == 0)   // the host's wait ends, then reads tmo
             __hip_atomic_store(reinterpret_cast<unsigned*>(ho.p), ho.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     } else if (flags & MPPI_FLAG_FUSED_UPDATE) {
-        nominal_update_block<NT>(nxt, c, sm, u_cur, u_first, upd, ho);
+        nominal_update_block<NT, CLAMP>(nxt, c, sm, u_cur, u_first, upd, ho, cl);
     }
     STAMP(7, NOW());
 }
 
 // Merge of the all-gathered per-device rows (multi-GPU), plus the fused update.
-template <int NT>
+template <int NT, bool CLAMP>
 __global__ __launch_bounds__(NT) void merge_kernel(const KConst c, const double* parts, int n, double* w_eps_out,
                                                    const DevStep* cur, DevStep* nxt, unsigned flags, float* upd,
-                                                   const HostOut ho) {
+                                                   const HostOut ho, const ClampK cl) {
     __shared__ Scratch sm;
     const int tid = threadIdx.x;
     const double u_cur = (flags & MPPI_FLAG_FUSED_UPDATE) ? nominal_src(cur, tid, c.T) : 0.0;
@@ -627,7 +673,7 @@ __global__ __launch_bounds__(NT) void merge_kernel(const KConst c, const double*
     const __amdgpu_buffer_rsrc_t r = rows_rsrc(parts, n * (2 + 2 * c.T) * 8);
     merge_rows_block<NT, 1, true, false>(r, 0, n, RowGeo(2 * c.T), c.inv_lambda, sm, nullptr, 0, nullptr, w_eps_out,
                                          0u, nullptr);
-    if (flags & MPPI_FLAG_FUSED_UPDATE) nominal_update_block<NT>(nxt, c, sm, u_cur, u_first, upd, ho);
+    if (flags & MPPI_FLAG_FUSED_UPDATE) nominal_update_block<NT, CLAMP>(nxt, c, sm, u_cur, u_first, upd, ho, cl);
 }
 
 // Trajectory re-roll (control.py:129-145): control(t) = base[(t-1) mod T] (+ eps).
@@ -639,11 +685,12 @@ __global__ __launch_bounds__(NT) void merge_kernel(const KConst c, const double*
 constexpr int kTrajTB = 8;
 // base: the controls, float2 elements bstride apart (1: a plain [T][2] array;
 // 2: the (u, a) float4 rows of a DevStep, read in place)
-template <bool NOISE>
+// CLAMP (clamp_mode >= 1): the control fed to _F is clipped, _g(u[t-1]) / _g(v[k, t-1]) of control.py:133,143.
+template <bool NOISE, bool CLAMP>
 __global__ __launch_bounds__(kThreads) void traj_kernel(const KConst c, const StepStatic ss,
                                                         const float2* __restrict__ base, int bstride,
                                                         const float2* __restrict__ noise, int Kn,
-                                                        float4* __restrict__ out) {
+                                                        float4* __restrict__ out, const ClampK cl) {
     __shared__ float4 tile[kTrajTB][kThreads];
     const int tid = threadIdx.x;
     const int k0 = blockIdx.x * kThreads;
@@ -653,7 +700,8 @@ __global__ __launch_bounds__(kThreads) void traj_kernel(const KConst c, const St
     const float exf = NOISE ? ((c.k_offset + k) < c.k_exploit ? 1.f : 0.f) : 1.f;
     Arm x;
     arm_init(x, ss.x0);
-    const DynK dk = make_dynk(c, 0.f, 0.f);
+    DynK dk = make_dynk(c, 0.f, 0.f);
+    if constexpr (CLAMP) dynk_limits(dk, cl);
     // the noise of a whole tile is loaded two tiles ahead (a lane's per-step load
     // would otherwise be waited for every step: one wave per SIMD hides nothing)
     auto load_tile = [&](int t0, float2 (&d)[kTrajTB]) {
@@ -675,6 +723,7 @@ __global__ __launch_bounds__(kThreads) void traj_kernel(const KConst c, const St
             const float2 b = base[ti * bstride];
             f32x2 v = {b.x, b.y};
             if (NOISE) v = __builtin_elementwise_fma(splat(exf), v, f32x2{cur[j].x, cur[j].y});
+            if constexpr (CLAMP) v = clamp_v(v, dk);
             arm_step(x, v, dk);
             const f32x2 q = x.Q * 6.283185307179586f;
             tile[j][tid] = make_float4(q.x, q.y, x.dq.x, x.dq.y);
@@ -711,7 +760,8 @@ __global__ __launch_bounds__(kThreads) void traj_kernel(const KConst c, const St
 __global__ __launch_bounds__(kThreads) void nearest_debug_kernel(const KConst c, const StepStatic ss,
                                                                  const DevStep* __restrict__ st,
                                                                  const float2* __restrict__ noise, int Kn,
-                                                                 int* __restrict__ slot, float2* __restrict__ pos) {
+                                                                 int* __restrict__ slot, float2* __restrict__ pos,
+                                                                 const ClampK cl) {
     const int k = blockIdx.x * kThreads + threadIdx.x;
     if (k >= Kn) return;
     const int T = c.T;
@@ -720,11 +770,15 @@ __global__ __launch_bounds__(kThreads) void nearest_debug_kernel(const KConst c,
     sr.load(ss.key, ss.ctr, 0);
     Arm x;
     arm_init(x, ss.x0);
-    const DynK dk = make_dynk(c, sr.cx, sr.cy);
+    DynK dk = make_dynk(c, sr.cx, sr.cy);
+    dynk_limits(dk, cl);
+    const bool clampv = cl.mode != 0;
     for (int t = 0; t < T; ++t) {
         const float4 ua = st->ua[t];
         const float2 e = noise[(size_t)t * c.K_local + k];
-        arm_step(x, __builtin_elementwise_fma(splat(exf), f32x2{ua.x, ua.y}, f32x2{e.x, e.y}), dk);
+        f32x2 v = __builtin_elementwise_fma(splat(exf), f32x2{ua.x, ua.y}, f32x2{e.x, e.y});
+        if (clampv) v = clamp_v(v, dk);   // as the rollout's CLAMP kernels
+        arm_step(x, v, dk);
         const f32x2 p = arm_fk(x, dk);
         const f32x2 d = p - dk.ctr;
         slot[(size_t)k * T + t] = (int)sr.nearest_d(d.x, d.y);
@@ -763,6 +817,7 @@ struct mppi_ctx {
     hipStream_t stream = nullptr;
     int lps = 1, nt = 256, nblocks = 0;
     KConst kc;
+    ClampK ck{};                // torque limits (mode 0: none)
     StepStatic stat{};          // x0 + window of the next launch (a kernel argument)
     DevStep* d_step = nullptr;  // [2] ping-pong nominal
     int cur = 0;
@@ -800,9 +855,11 @@ namespace {
 using mppi_host::fail;
 using mppi_host::launch_check;
 
+// of the kernel the context will launch: the CLAMP form holds two more register pairs
 template <int L, int N>
-int occupancy(int* per_cu) {
-    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (const void*)rollout_kernel<L, N, true>, N, 0);
+int occupancy(int* per_cu, bool clamp) {
+    const void* f = clamp ? (const void*)rollout_kernel<L, N, true, true> : (const void*)rollout_kernel<L, N, true, false>;
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, N, 0);
 }
 
 int check_timeout(mppi_ctx* c) {
@@ -847,15 +904,16 @@ int alloc(mppi_ctx* c) {
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
     {
         const int lps = c->lps;
+        const bool cl = c->ck.mode != 0;
         int rc = 0;
         if (c->nt == 512)
-            rc = lps == 1 ? occupancy<1, 512>(&per_cu) : lps == 2 ? occupancy<2, 512>(&per_cu)
-               : lps == 4 ? occupancy<4, 512>(&per_cu) : lps == 8 ? occupancy<8, 512>(&per_cu)
-               : occupancy<16, 512>(&per_cu);
+            rc = lps == 1 ? occupancy<1, 512>(&per_cu, cl) : lps == 2 ? occupancy<2, 512>(&per_cu, cl)
+               : lps == 4 ? occupancy<4, 512>(&per_cu, cl) : lps == 8 ? occupancy<8, 512>(&per_cu, cl)
+               : occupancy<16, 512>(&per_cu, cl);
         else
-            rc = lps == 1 ? occupancy<1, 256>(&per_cu) : lps == 2 ? occupancy<2, 256>(&per_cu)
-               : lps == 4 ? occupancy<4, 256>(&per_cu) : lps == 8 ? occupancy<8, 256>(&per_cu)
-               : occupancy<16, 256>(&per_cu);
+            rc = lps == 1 ? occupancy<1, 256>(&per_cu, cl) : lps == 2 ? occupancy<2, 256>(&per_cu, cl)
+               : lps == 4 ? occupancy<4, 256>(&per_cu, cl) : lps == 8 ? occupancy<8, 256>(&per_cu, cl)
+               : occupancy<16, 256>(&per_cu, cl);
         if (rc != 0) per_cu = 0;
     }
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + 2 * c->cfg.T, 0)) return rc;
@@ -896,6 +954,13 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
     *out = nullptr;
     if (cfg->T < 1 || cfg->T > MPPI_MAX_T) return fail(MPPI_E_ARG, "T must be in [1, 128]");
     if (int rc = mppi_host::check_sample_geometry(cfg->K_local, cfg->K_total, cfg->k_offset)) return rc;
+    if (cfg->clamp_mode < 0 || cfg->clamp_mode > 2) return fail(MPPI_E_ARG, "clamp_mode must be 0, 1 or 2");
+    if (cfg->clamp_mode > 0)
+        for (int d = 0; d < 2; ++d) {
+            if (isnan(cfg->u_min[d])) return fail(MPPI_E_ARG, "u_min: a limit is NaN (use -inf for no limit)");
+            if (isnan(cfg->u_max[d])) return fail(MPPI_E_ARG, "u_max: a limit is NaN (use +inf for no limit)");
+            if (cfg->u_min[d] > cfg->u_max[d]) return fail(MPPI_E_ARG, "u_min[d] > u_max[d]: the limits are crossed");
+        }
     const double* S = cfg->sigma;
     const double det = S[0] * S[3] - S[1] * S[2];
     if (det == 0.0 || !isfinite(det)) return fail(MPPI_E_SINGULAR, "Singular matrix");
@@ -943,6 +1008,16 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
         k.tw[i] = (float)(cfg->terminal_cost_weight[i] * 10000.0);  // control.py:198
     }
     for (int i = 0; i < 4; ++i) k.sig_inv[i] = c->sig_inv[i];
+    ClampK& ck = c->ck;
+    ck.mode = cfg->clamp_mode;
+    for (int d = 0; d < 2; ++d) {
+        // without limits the fields are never read; the sample clamp runs in fp32 like the rest of the
+        // rollout, on the limits rounded to nearest (monotonic, so v_lo <= v_hi still)
+        ck.u_lo[d] = cfg->clamp_mode ? cfg->u_min[d] : -INFINITY;
+        ck.u_hi[d] = cfg->clamp_mode ? cfg->u_max[d] : INFINITY;
+        ck.v_lo[d] = (float)ck.u_lo[d];
+        ck.v_hi[d] = (float)ck.u_hi[d];
+    }
 
     if (int rc = alloc(c)) {
         mppi_ctx_destroy(c);
@@ -1088,6 +1163,15 @@ void host_F(const mppi_arm_params& a, double dt, double* x, double u1, double u2
     x[1] = q2 + x[3] * dt;
 }
 
+// The trajectory re-roll of samples [0, K): with noise the sampled one, with torque limits the clipping one.
+void launch_traj(mppi_ctx* c, int blocks, const float2* base, int bstride, const float2* noise, int K, float4* out) {
+    const bool cl = c->ck.mode != 0;
+    auto* f = noise ? (cl ? traj_kernel<true, true> : traj_kernel<true, false>)
+                    : (cl ? traj_kernel<false, true> : traj_kernel<false, false>);
+    hipLaunchKernelGGL(f, dim3(blocks), dim3(kThreads), 0, c->stream, c->kc, c->stat, base, bstride, noise, K, out,
+                       c->ck);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1119,14 +1203,20 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
     const DevStep* cur = c->d_step + c->cur;
     DevStep* nxt = c->d_step + (c->cur ^ 1);
     const float2* nz = reinterpret_cast<const float2*>(noise_dev);
-#define MPPI_LAUNCH(L, NTH, P)                                                                                   \
-    hipLaunchKernelGGL((rollout_kernel<L, NTH, P>), dim3(c->nblocks), dim3(NTH), 0, c->stream, c->kc, c->stat, cur, nz, \
+#define MPPI_LAUNCH(L, NTH, P, CL)                                                                               \
+    hipLaunchKernelGGL((rollout_kernel<L, NTH, P, CL>), dim3(c->nblocks), dim3(NTH), 0, c->stream, c->kc, c->stat, cur, nz, \
                        S_dev, c->hand.d_slab, c->hand.d_gslab, c->hand.d_counter, partial_dev, c->d_weps, nxt, flags,  \
-                       c->ex.xd, c->hand.d_epoch, c->hand.d_tmo, reinterpret_cast<float*>(c->d_upd), ho, c->d_dbg)
+                       c->ex.xd, c->hand.d_epoch, c->hand.d_tmo, reinterpret_cast<float*>(c->d_upd), ho, c->d_dbg, \
+                       c->ck)
+#define MPPI_LAUNCH_C(L, NTH, P)                            \
+    do {                                                    \
+        if (c->ck.mode != 0) MPPI_LAUNCH(L, NTH, P, true);  \
+        else MPPI_LAUNCH(L, NTH, P, false);                 \
+    } while (0)
 #define MPPI_LAUNCH_P(L, NTH)                \
     do {                                     \
-        if (c->hand.poll) MPPI_LAUNCH(L, NTH, true);  \
-        else MPPI_LAUNCH(L, NTH, false);     \
+        if (c->hand.poll) MPPI_LAUNCH_C(L, NTH, true);  \
+        else MPPI_LAUNCH_C(L, NTH, false);   \
     } while (0)
     if (c->nt == 512) {
         if (c->lps == 1) MPPI_LAUNCH_P(1, 512);
@@ -1142,6 +1232,7 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
         else MPPI_LAUNCH_P(16, 256);
     }
 #undef MPPI_LAUNCH_P
+#undef MPPI_LAUNCH_C
 #undef MPPI_LAUNCH
     const int rc = launch_check("rollout_kernel");
     if (rc == MPPI_OK && (flags & MPPI_FLAG_FUSED_UPDATE)) {
@@ -1177,12 +1268,11 @@ int mppi_merge_partials(mppi_ctx* c, const double* partials_dev, int n, unsigned
     DevStep* nxt = c->d_step + (c->cur ^ 1);
     const HostOut ho = next_host_out(c, flags);
     // one workgroup, one thread per merged column (2T + 1 <= 256 up to T = 127)
-    if (2 * c->cfg.T + 1 <= 256)
-        hipLaunchKernelGGL(merge_kernel<256>, dim3(1), dim3(256), 0, c->stream, c->kc, partials_dev, n, c->d_weps,
-                           cur, nxt, flags, reinterpret_cast<float*>(c->d_upd), ho);
-    else
-        hipLaunchKernelGGL(merge_kernel<512>, dim3(1), dim3(512), 0, c->stream, c->kc, partials_dev, n, c->d_weps,
-                           cur, nxt, flags, reinterpret_cast<float*>(c->d_upd), ho);
+    const bool big = 2 * c->cfg.T + 1 > 256, cl = c->ck.mode != 0;
+    auto* f = big ? (cl ? merge_kernel<512, true> : merge_kernel<512, false>)
+                  : (cl ? merge_kernel<256, true> : merge_kernel<256, false>);
+    hipLaunchKernelGGL(f, dim3(1), dim3(big ? 512 : 256), 0, c->stream, c->kc, partials_dev, n, c->d_weps, cur, nxt,
+                       flags, reinterpret_cast<float*>(c->d_upd), ho, c->ck);
     const int rc = launch_check("merge_kernel");
     if (rc == MPPI_OK && (flags & MPPI_FLAG_FUSED_UPDATE)) {
         c->cur ^= 1;
@@ -1229,20 +1319,14 @@ int mppi_rollout_traj(mppi_ctx* c, const double* base_u, const float* noise_dev,
         bstride = 2;
     }
     const int blocks = (K + kThreads - 1) / kThreads;
-    if (noise_dev)
-        hipLaunchKernelGGL(traj_kernel<true>, dim3(blocks), dim3(kThreads), 0, c->stream, c->kc, c->stat, base, bstride,
-                           reinterpret_cast<const float2*>(noise_dev), K, reinterpret_cast<float4*>(out_dev));
-    else
-        hipLaunchKernelGGL(traj_kernel<false>, dim3(blocks), dim3(kThreads), 0, c->stream, c->kc, c->stat, base,
-                           bstride, (const float2*)nullptr, K, reinterpret_cast<float4*>(out_dev));
+    launch_traj(c, blocks, base, bstride, reinterpret_cast<const float2*>(noise_dev), K, reinterpret_cast<float4*>(out_dev));
     return launch_check("traj_kernel");
 }
 
 int mppi_optimal_traj(mppi_ctx* c, float* out_dev) {
     if (!c || !out_dev) return fail(MPPI_E_ARG, "null argument");
     if (!c->upd_valid) return fail(MPPI_E_ARG, "mppi_optimal_traj needs a preceding MPPI_FLAG_FUSED_UPDATE launch");
-    hipLaunchKernelGGL(traj_kernel<false>, dim3(1), dim3(kThreads), 0, c->stream, c->kc, c->stat, c->d_upd, 1,
-                       (const float2*)nullptr, 1, reinterpret_cast<float4*>(out_dev));
+    launch_traj(c, 1, c->d_upd, 1, nullptr, 1, reinterpret_cast<float4*>(out_dev));
     return launch_check("traj_kernel");
 }
 
@@ -1265,9 +1349,15 @@ int mppi_optimal_traj_host(const mppi_ctx* c, const double* x0, const double* u_
     // control.py:129-134: x_{t+1} = _F(x_t, u_new[t - 1]), u_new[-1] = u_new[T - 1]
     const int T = c->cfg.T;
     double x[4] = {x0[0], x0[1], x0[2], x0[3]};
+    const ClampK& k = c->ck;
     for (int t = 0; t < T; ++t) {
         const double* ut = u_new + 2 * (t == 0 ? T - 1 : t - 1);
-        host_F(c->cfg.arm, c->cfg.delta_t, x, ut[0], ut[1]);
+        double u0 = ut[0], u1 = ut[1];
+        if (k.mode >= 1) {   // _g(u[t-1]), control.py:133, on a copy (a nominal the device clipped stays as it is)
+            u0 = clamp_u(u0, k.u_lo[0], k.u_hi[0]);
+            u1 = clamp_u(u1, k.u_lo[1], k.u_hi[1]);
+        }
+        host_F(c->cfg.arm, c->cfg.delta_t, x, u0, u1);
         memcpy(traj_out + 4 * t, x, sizeof(x));
     }
     return MPPI_OK;
@@ -1435,7 +1525,7 @@ int mppi_debug_nearest(mppi_ctx* c, const float* noise_dev, int K, int* slot_dev
     if (!c || !noise_dev || !slot_dev || !pos_dev || K < 1 || K > c->cfg.K_local) return fail(MPPI_E_ARG, "bad argument");
     hipLaunchKernelGGL(nearest_debug_kernel, dim3((K + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, c->kc,
                        c->stat, c->d_step + c->cur, reinterpret_cast<const float2*>(noise_dev), K, slot_dev,
-                       reinterpret_cast<float2*>(pos_dev));
+                       reinterpret_cast<float2*>(pos_dev), c->ck);
     return launch_check("nearest_debug_kernel");
 }
 

@@ -283,8 +283,21 @@ class RolloutEngine(_Engine):
                  sigma, stage_cost_weight, terminal_cost_weight, param_exploration: float = 0.0,
                  arm: ArmParams = ArmParams(), K_total: int | None = None, k_offset: int = 0,
                  device: int | torch.device | None = None, lanes_per_sample: int = 0,
-                 param_gamma: float | None = None):
+                 param_gamma: float | None = None, u_min=None, u_max=None, clamp_nominal: bool = True):
+        """u_min / u_max: torque limits per control component (a scalar or two values; None or +-inf: no
+        limit on that side), the reference's clamp hook _g (control.py:166-172) switched on.  Every sampled
+        control is clipped before the dynamics and the control cost, the re-rolled trajectories clip theirs,
+        and with clamp_nominal (the reference with visualize_optimal_traj) the fused update clips the nominal
+        too.  The context rejects NaN limits and u_min > u_max (ValueError)."""
         cfg = N.ConfigC()
+        cfg.clamp_mode = self.clamp_mode(u_min, u_max, clamp_nominal)
+        if cfg.clamp_mode:
+            lo = np.broadcast_to(np.asarray(-np.inf if u_min is None else u_min, dtype=np.float64), (2,))
+            hi = np.broadcast_to(np.asarray(np.inf if u_max is None else u_max, dtype=np.float64), (2,))
+            for d in range(2):
+                cfg.u_min[d], cfg.u_max[d] = float(lo[d]), float(hi[d])
+        self.u_min = None if not cfg.clamp_mode else np.array(cfg.u_min)
+        self.u_max = None if not cfg.clamp_mode else np.array(cfg.u_max)
         cfg.delta_t = float(delta_t)
         cfg.param_lambda = float(param_lambda)
         cfg.param_alpha = float(param_alpha)
@@ -310,6 +323,13 @@ class RolloutEngine(_Engine):
         N.check(self._lib.mppi_ctx_handoff(self._ctx, C.byref(poll)), "mppi_ctx_handoff")
         # in-launch hand-off of the workgroup partials: "poll" (tagged granules) or "counter"
         self.handoff = "poll" if poll.value else "counter"
+
+    @staticmethod
+    def clamp_mode(u_min, u_max, clamp_nominal: bool) -> int:
+        """mppi_config.clamp_mode: 0 without limits, 2 with them, 1 with them and clamp_nominal off."""
+        if u_min is None and u_max is None:
+            return 0
+        return 2 if clamp_nominal else 1
 
     def merge(self, partials: torch.Tensor, n: int, fused_update: bool = False, host_out: bool = False) -> None:
         super().merge(partials, n, fused_update, N.MPPI_FLAG_HOST_OUT if host_out else 0)   # host_out: the arm only
