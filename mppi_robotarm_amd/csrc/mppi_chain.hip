@@ -891,7 +891,7 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
     return q_sum_f64(S);
 }
 
-// POLL / counter hand-off and the merges as in rollout_kernel (mppi_rocm.hip).
+// POLL / counter: the hand-off form of the partial rows (handoff_merge in mppi_device.h, shared with rollout_kernel).
 // SLOTS (debug instances, mppi_chain_debug_slots): dbg receives the window slot
 // each sample picked at each step, int32 [k][t].
 template <int N, bool POLL, bool F64, int LPS, bool SLOTS = false>
@@ -1033,18 +1033,8 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     unsigned long long run0 = ~0ull;
     if (kEarlyRun && tid == 0) run0 = __hip_atomic_load(runmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const double rho_b = block_min_f64<kCT>(owner ? S : INFINITY, sm);
-    // fp64, like the reference's weights; a wave whose samples all lie below the
-    // floor (exp(-44.4) = 2^-64: the usual case, S spread >> lambda) skips the exp
-    const double warg = (rho_b - S) * c.inv_lambda;
-    double wgt = 0.0;
-    if (__any(owner && warg >= -45.0)) wgt = owner ? exp(warg) : 0.0;
-    const bool nz = wgt >= kMergeFloor;
-    const unsigned long long bal = __ballot(nz);
-    const double esum = wave_sum_f64(nz ? wgt : 0.0);
-    if (lane == 0) {
-        s_cnt[wave] = __popcll(bal);
-        s_redd[wave] = esum;
-    }
+    // the epilogue's stages: mppi_device.h, "the rollout epilogue"
+    const LaneWeight lw = block_weigh(owner, S, rho_b, c.inv_lambda, lane, wave, s_cnt, s_redd);
     // The running minimum of the workgroups' rho_b (one 64-bit atomic min per
     // workgroup on an order-preserving key; reset by the final merger).  The final
     // rho is at most any minimum over published rho_b, so a workgroup whose rho_b
@@ -1065,19 +1055,8 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     __syncthreads();
     const bool skip = exp((s_run - rho_b) * c.inv_lambda) < kMergeFloor;   // uniform
-    int off = 0, nl = 0;
-    double eta_b = 0.0;
-#pragma unroll
-    for (int w = 0; w < kCT / 64; ++w) {
-        off += (w < wave) ? s_cnt[w] : 0;
-        nl += s_cnt[w];
-        eta_b += s_redd[w];
-    }
-    if (nz) {
-        const int pos = off + lanes_below(bal);
-        s_k[pos] = k;
-        s_e[pos] = wgt;
-    }
+    double eta_b;
+    int nl = block_compact<kCT>(lw, k, wave, s_cnt, s_redd, s_k, s_e, &eta_b);
     __syncthreads();
     // past the barriers (a barrier's fence would wait for the atomic to complete): fire and forget; the
     // gather's loads, issued after it, return after it anyway
@@ -1095,7 +1074,8 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if constexpr (POLL) st_gran(slab_r, idx, v, tag);
         else st_wt(slab_r, idx, v);
     };
-    // rho_b and eta_b leave first (see rollout_kernel in mppi_rocm.hip)
+    // rho_b and eta_b leave first, together: rho_b waits for the skip test (rollout_kernel publishes its own
+    // straight after the block minimum)
     nl = __builtin_amdgcn_readfirstlane(nl);
     if (tid == 0) {
         publish(blockIdx.x * stride, skip ? INFINITY : rho_b);
@@ -1114,16 +1094,8 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         constexpr int PER = (NS + 63) / 64;
         constexpr int kRowBatch = 4;
         const int k0 = blockIdx.x * NS;
-        if (tid < NS) s_e[tid] = 0.0;
-        __syncthreads();
-        if (nz) s_e[k - k0] = wgt;
-        __syncthreads();
         double w[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int ks = lane + 64 * i;
-            w[i] = (ks < NS && k0 + ks < K) ? s_e[ks] : 0.0;
-        }
+        dense_weights<kCT, NS>(lw, k, K, s_e, w);
         for (int cb = wave * kRowBatch; cb < nval; cb += (kCT / 64) * kRowBatch) {
             float e[kRowBatch][PER];
 #pragma unroll
@@ -1147,45 +1119,11 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     STAMP(2, NOW());
     STAMP(5, (unsigned long long)nl);
-    const int g = blockIdx.x / kGroup;
-    const int gsz = min(kGroup, nrows - g * kGroup);
-    if constexpr (POLL) {
-        if ((int)blockIdx.x != g * kGroup) return;
-        STAMP(3, NOW());
-        if (ngroups == 1) {
-            merge_rows_block<kCT, kCMaxCh, true, true>(slab_r, 0, gsz, geo, c.inv_lambda, sm, nullptr, 0, partial_out,
-                                                       w_eps_out, tag, tmo);
-        } else if (blockIdx.x == 0 && nrows <= kDirectRows &&
-                   direct_merge<kCT, kCMaxCh, true>(slab_r, nrows, geo, c.inv_lambda, sm, partial_out, w_eps_out, tag,
-                                                    tmo)) {
-        } else {
-            merge_rows_block<kCT, kCMaxCh, false, true>(slab_r, g * kGroup, gsz, geo, c.inv_lambda, sm, &gslab_r, g,
-                                                        nullptr, nullptr, tag, tmo);
-            STAMP(10, NOW());
-            if (blockIdx.x != 0) return;
-            STAMP(4, NOW());
-            merge_rows_block<kCT, kCMaxCh, true, true>(gslab_r, 0, ngroups, geo, c.inv_lambda, sm, nullptr, 0,
-                                                       partial_out, w_eps_out, tag, tmo);
-        }
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(epoch, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(runmin, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every row is in
-        }
-    } else {
-        if (!arrive_last(counters + g, (unsigned)gsz, &s_flag, c.acquire != 0)) return;
-        STAMP(3, NOW());
-        merge_rows_block<kCT, kCMaxCh, false, false>(slab_r, g * kGroup, gsz, geo, c.inv_lambda, sm, &gslab_r, g,
-                                                     nullptr, nullptr, 0u, nullptr);
-        STAMP(10, NOW());
-        if (!arrive_last(counters + ngroups, (unsigned)ngroups, &s_flag, c.acquire != 0)) return;
-        STAMP(4, NOW());
-        if (!(ngroups > 1 && nrows <= kDirectRows &&
-              direct_merge<kCT, kCMaxCh, false>(slab_r, nrows, geo, c.inv_lambda, sm, partial_out, w_eps_out, 0u,
-                                                nullptr)))
-            merge_rows_block<kCT, kCMaxCh, true, false>(gslab_r, 0, ngroups, geo, c.inv_lambda, sm, nullptr, 0,
-                                                        partial_out, w_eps_out, 0u, nullptr);
-        if (threadIdx.x == 0) __hip_atomic_store(runmin, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (!handoff_merge<kCT, kCMaxCh, POLL>(slab_r, gslab_r, nrows, geo, c.inv_lambda, sm, counters, c.acquire != 0, &s_flag,
+                                           partial_out, w_eps_out, tag, epoch, tmo, dbg, nullptr))
+        return;
+    // every row is in: the running minimum is reset for the next launch
+    if (threadIdx.x == 0) __hip_atomic_store(runmin, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     STAMP(11, NOW());
     STAMP(6, (unsigned long long)sm.nrel);
     // with the exchange, the update is computed while the ranks' statuses travel: it lands in the ping-pong
@@ -1379,17 +1317,45 @@ void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise,
                        c->d_runmin, c->d_dbg);
 }
 
-// the link counts with an instantiated kernel
-#define MPPI_CHAIN_DISPATCH(n, F) \
-    switch (n) {                  \
-        case 2: F(2); break;      \
-        case 3: F(3); break;      \
-        case 4: F(4); break;      \
-        case 5: F(5); break;      \
-        case 6: F(6); break;      \
-        case 7: F(7); break;      \
-        default: break;           \
-    }
+// the link counts with an instantiated kernel: f(N) for N = n as an integral constant
+template <class F>
+void with_links(int n, F&& f) {
+    mppi_host::with_value<2, 3, 4, 5, 6, 7>(n, f);
+}
+
+// The instantiated rollout kernels: links x POLL x (fp64 at one lane per sample, fp32 at one or four).  Calls
+// f(n, poll, f64, lps), the context's instance as integral constants, in the hand-off form `poll`.
+template <class F>
+void with_rollout(const mppi_chain_ctx* c, bool poll, F&& f) {
+    using L1 = std::integral_constant<int, 1>;
+    using L4 = std::integral_constant<int, 4>;
+    with_links(c->n, [&](auto n) {
+        mppi_host::with_bool(poll, [&](auto p) {
+            if (c->f64) f(n, p, std::true_type{}, L1{});
+            else if (c->lps == 4) f(n, p, std::false_type{}, L4{});
+            else f(n, p, std::false_type{}, L1{});
+        });
+    });
+}
+
+// After a launch: a fused update made the other ping-pong block current.
+void note_update(mppi_chain_ctx* c, unsigned flags) {
+    const bool upd = (flags & MPPI_FLAG_FUSED_UPDATE) != 0;
+    if (upd) c->cur ^= 1;
+    c->x_flipped = upd && (flags & MPPI_FLAG_EXCHANGE);   // undone on MPPI_E_EXCHANGE
+    c->upd_valid = upd;
+    if (upd) c->pub_valid = false;
+}
+
+// Queues the read-back of the current block's update into h_out: the shifted nominal, then {u_first, eta}.
+int queue_update_readback(mppi_chain_ctx* c) {
+    const char* blk = (const char*)(c->d_step + c->cur);
+    HIP_TRY(hipMemcpyAsync(c->h_out, blk + offsetof(ChainStep, u), (size_t)c->cfg.T * kCMax * sizeof(double),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_out + kCMaxVals, blk + offsetof(ChainStep, u_first), (kCMax + 1) * sizeof(double),
+                           hipMemcpyDeviceToHost, c->stream));
+    return MPPI_OK;
+}
 
 // Lanes per sample of the fp32 rollout: 4 while one lane per sample would leave
 // SIMDs without a wave (K <= 32768: at most 512 waves of 64 samples on 1024 SIMDs);
@@ -1422,15 +1388,9 @@ int alloc(mppi_chain_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     int ncu = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-#define MPPI_OCC(N)                                                                                          \
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(                                                      \
-        &per_cu,                                                                                             \
-        c->f64 ? (const void*)chain_rollout_kernel<N, true, true, 1>                                          \
-               : (c->lps == 4 ? (const void*)chain_rollout_kernel<N, true, false, 4>                          \
-                              : (const void*)chain_rollout_kernel<N, true, false, 1>),                        \
-        kCT, 0)
-    MPPI_CHAIN_DISPATCH(c->n, MPPI_OCC)
-#undef MPPI_OCC
+    with_rollout(c, true, [&](auto n, auto p, auto f64, auto lps) {   // always of the POLL form
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps>, kCT, 0);
+    });
     // behind the counters: the per-CU ticket words of the issue fairness (mppi_device.h)
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + c->cfg.T * c->n, kCuSlots)) return rc;
     c->kc.acquire = c->hand.acquire;
@@ -1663,31 +1623,16 @@ int chain_rollout(mppi_chain_ctx* c, const float* noise_dev, double* S_dev, doub
     }
     const ChainStep* cur = c->d_step + c->cur;
     ChainStep* nxt = c->d_step + (c->cur ^ 1);
-#define MPPI_L(N)                                                                       \
-    if (c->f64) {                                                                       \
-        if (c->hand.poll) launch_rollout<N, true, true, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
-        else launch_rollout<N, false, true, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
-    } else if (c->lps == 4) {                                                           \
-        if (c->hand.poll) launch_rollout<N, true, false, 4>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
-        else launch_rollout<N, false, false, 4>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
-    } else if (c->hand.poll) launch_rollout<N, true, false, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots); \
-    else launch_rollout<N, false, false, 1>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots)
-    MPPI_CHAIN_DISPATCH(c->n, MPPI_L)
-#undef MPPI_L
+    with_rollout(c, c->hand.poll, [&](auto n, auto p, auto f64, auto lps) {
+        launch_rollout<n, p, f64, lps>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots);
+    });
     if (int rc = launch_check("chain_rollout_kernel")) return rc;
-    if (flags & MPPI_FLAG_FUSED_UPDATE) c->cur ^= 1;
-    c->x_flipped = (flags & MPPI_FLAG_FUSED_UPDATE) && (flags & MPPI_FLAG_EXCHANGE);   // undone on MPPI_E_EXCHANGE
-    c->upd_valid = (flags & MPPI_FLAG_FUSED_UPDATE) != 0;
-    if (flags & MPPI_FLAG_FUSED_UPDATE) c->pub_valid = false;
+    note_update(c, flags);
     c->out_posted = false;
     if ((flags & MPPI_FLAG_FUSED_UPDATE) && (flags & MPPI_FLAG_HOST_OUT)) {
         // the update's read-back right behind the launch, so what the caller queues next (the next
         // step's noise) does not delay mppi_chain_wait_outputs
-        const char* blk = (const char*)(c->d_step + c->cur);
-        HIP_TRY(hipMemcpyAsync(c->h_out, blk + offsetof(ChainStep, u), (size_t)c->cfg.T * kCMax * sizeof(double),
-                               hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->h_out + kCMaxVals, blk + offsetof(ChainStep, u_first), (kCMax + 1) * sizeof(double),
-                               hipMemcpyDeviceToHost, c->stream));
+        if (int rc = queue_update_readback(c)) return rc;
         HIP_TRY(hipEventRecord(c->out_ev, c->stream));
         c->out_posted = true;
     }
@@ -1725,16 +1670,12 @@ int mppi_chain_merge_partials(mppi_chain_ctx* c, const double* partials_dev, int
         return fail(MPPI_E_ARG, "device median filter needs T >= 5 (use the host update)");
     const ChainStep* cur = c->d_step + c->cur;
     ChainStep* nxt = c->d_step + (c->cur ^ 1);
-#define MPPI_M(N)                                                                                              \
-    hipLaunchKernelGGL(chain_merge_kernel<N>, dim3(1), dim3(kCT), 0, c->stream, c->kc, cur, partials_dev, nparts, \
-                       c->d_weps, nxt, flags)
-    MPPI_CHAIN_DISPATCH(c->n, MPPI_M)
-#undef MPPI_M
+    with_links(c->n, [&](auto n) {
+        hipLaunchKernelGGL(chain_merge_kernel<n>, dim3(1), dim3(kCT), 0, c->stream, c->kc, cur, partials_dev, nparts,
+                           c->d_weps, nxt, flags);
+    });
     if (int rc = launch_check("chain_merge_kernel")) return rc;
-    if (flags & MPPI_FLAG_FUSED_UPDATE) c->cur ^= 1;
-    c->x_flipped = (flags & MPPI_FLAG_FUSED_UPDATE) && (flags & MPPI_FLAG_EXCHANGE);   // undone on MPPI_E_EXCHANGE
-    c->upd_valid = (flags & MPPI_FLAG_FUSED_UPDATE) != 0;
-    if (flags & MPPI_FLAG_FUSED_UPDATE) c->pub_valid = false;
+    note_update(c, flags);
     return MPPI_OK;
 }
 
@@ -1815,11 +1756,7 @@ int mppi_chain_wait_outputs(mppi_chain_ctx* c, const double* x0, double* u_out, 
     if (c->out_posted) {   // MPPI_FLAG_HOST_OUT: the copy is already queued behind the launch
         HIP_TRY(hipEventSynchronize(c->out_ev));
     } else {
-        const char* blk = (const char*)(c->d_step + c->cur);
-        HIP_TRY(hipMemcpyAsync(c->h_out, blk + offsetof(ChainStep, u), (size_t)T * kCMax * sizeof(double),
-                               hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->h_out + kCMaxVals, blk + offsetof(ChainStep, u_first), (kCMax + 1) * sizeof(double),
-                               hipMemcpyDeviceToHost, c->stream));
+        if (int rc = queue_update_readback(c)) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (int rc = check_tmo(c)) return rc;
@@ -1841,9 +1778,7 @@ int mppi_chain_wait_outputs(mppi_chain_ctx* c, const double* x0, double* u_out, 
 
 int mppi_chain_optimal_traj_host(mppi_chain_ctx* c, const double* x0, const double* u_new, double* traj_out) {
     if (!c || !x0 || !u_new || !traj_out) return fail(MPPI_E_ARG, "null argument");
-#define MPPI_TH(N) chain_traj_host<N>(c->h_dynd, x0, u_new, c->cfg.T, traj_out)
-    MPPI_CHAIN_DISPATCH(c->n, MPPI_TH);
-#undef MPPI_TH
+    with_links(c->n, [&](auto n) { chain_traj_host<n>(c->h_dynd, x0, u_new, c->cfg.T, traj_out); });
     return MPPI_OK;
 }
 
@@ -1862,28 +1797,22 @@ int mppi_chain_rollout_traj(mppi_chain_ctx* c, const double* base_u, const float
                                  2 * kCMax * sizeof(float), n * sizeof(float), T, hipMemcpyDeviceToDevice, c->stream));
     }
     const int blocks = (K + kCT - 1) / kCT;
-#define MPPI_T(N)                                                                                                \
-    do {                                                                                                         \
-        if (noise_dev)                                                                                           \
-            hipLaunchKernelGGL((chain_traj_kernel<N, true>), dim3(blocks), dim3(kCT), 0, c->stream, c->kc, cur,  \
-                               c->d_base, noise_dev, K, out_dev);                                                \
-        else                                                                                                     \
-            hipLaunchKernelGGL((chain_traj_kernel<N, false>), dim3(blocks), dim3(kCT), 0, c->stream, c->kc, cur, \
-                               c->d_base, noise_dev, K, out_dev);                                                \
-    } while (0)
-    MPPI_CHAIN_DISPATCH(n, MPPI_T)
-#undef MPPI_T
+    with_links(n, [&](auto nl) {
+        mppi_host::with_bool(noise_dev != nullptr, [&](auto noisy) {
+            hipLaunchKernelGGL((chain_traj_kernel<nl, noisy>), dim3(blocks), dim3(kCT), 0, c->stream, c->kc, cur,
+                               c->d_base, noise_dev, K, out_dev);
+        });
+    });
     return launch_check("chain_traj_kernel");
 }
 
 int mppi_chain_noise_philox(mppi_chain_ctx* c, unsigned long long seed, unsigned long long step, float* out_dev) {
     if (!c || !out_dev) return fail(MPPI_E_ARG, "null argument");
     const dim3 grid((unsigned)((c->cfg.K_local + kCT - 1) / kCT), (unsigned)c->cfg.T);
-#define MPPI_PH(N)                                                                                            \
-    hipLaunchKernelGGL(chain_philox_kernel<N>, grid, dim3(kCT), 0, c->stream, c->cfg.K_local, c->cfg.T,         \
-                       (long long)c->cfg.k_offset, seed, step, c->chol, out_dev)
-    MPPI_CHAIN_DISPATCH(c->n, MPPI_PH);
-#undef MPPI_PH
+    with_links(c->n, [&](auto n) {
+        hipLaunchKernelGGL(chain_philox_kernel<n>, grid, dim3(kCT), 0, c->stream, c->cfg.K_local, c->cfg.T,
+                           (long long)c->cfg.k_offset, seed, step, c->chol, out_dev);
+    });
     return launch_check("chain_philox_kernel");
 }
 

@@ -882,6 +882,143 @@ __device__ __forceinline__ bool arrive_last(unsigned* counter, unsigned expected
     return *s_flag != 0;
 }
 
+// ------------------------------------------------------- the rollout epilogue
+// Both rollout kernels (rollout_kernel, chain_rollout_kernel) end the same way: the samples' costs S become
+// the workgroup's partial row {rho_b, eta_b, N_b} (control.py:112-118 over the workgroup), which travels
+// through the two-level hand-off merge.  The stages below are that common text; the LDS arrays are the
+// kernels' own (declared there, so each kernel keeps its layout), and so are the barriers between the stages,
+// the publishing of rho_b and eta_b, the chain's running minimum and the gathers' row loads, which differ.
+
+// A lane's soft-min weight relative to the workgroup minimum, and its wave's ballot of the weights kept.
+struct LaneWeight {
+    double wgt;
+    bool nz;
+    unsigned long long bal;
+};
+
+// Weights exp((rho_b - S) / lambda) in fp64, like the reference's; those below 2^-64 of the workgroup's
+// best are dropped (see kMergeFloor), and a wave whose samples all lie below the floor (exp(-44.4) = 2^-64:
+// the usual case, S spread >> lambda) skips the exp.  Leaves each wave's count and sum of kept weights in
+// s_cnt / s_redd; the caller's barrier comes before block_compact.  lane, wave: the thread's, passed as the
+// kernel's own values (recomputed here they cost every instance two or three instructions).
+__device__ __forceinline__ LaneWeight block_weigh(bool owner, double S, double rho_b, double inv_lambda, int lane,
+                                                  int wave, int* s_cnt, double* s_redd) {
+    const double warg = (rho_b - S) * inv_lambda;
+    double wgt = 0.0;
+    if (__any(owner && warg >= -45.0)) wgt = owner ? exp(warg) : 0.0;
+    const bool nz = wgt >= kMergeFloor;
+    const unsigned long long bal = __ballot(nz);
+    const double esum = wave_sum_f64(nz ? wgt : 0.0);
+    if (lane == 0) {
+        s_cnt[wave] = __popcll(bal);
+        s_redd[wave] = esum;
+    }
+    return LaneWeight{wgt, nz, bal};
+}
+
+// The kept samples (index k, weight) in thread order into s_k / s_e; returns their number and sets eta_b,
+// the sum of their weights in wave order.  The caller's barrier comes before s_k / s_e are read.
+template <int NT>
+__device__ __forceinline__ int block_compact(const LaneWeight& lw, int k, int wave, const int* s_cnt,
+                                             const double* s_redd, int* s_k, double* s_e, double* eta_b) {
+    int off = 0, nl = 0;
+    double eta = 0.0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+        off += (w < wave) ? s_cnt[w] : 0;
+        nl += s_cnt[w];
+        eta += s_redd[w];
+    }
+    if (lw.nz) {
+        const int pos = off + lanes_below(lw.bal);
+        s_k[pos] = k;
+        s_e[pos] = lw.wgt;
+    }
+    *eta_b = eta;
+    return nl;
+}
+
+// Dense weights (more than kSparseMax kept samples): the weight of the workgroup's sample ks in s_e[ks]
+// (0 where dropped), then lane l's samples l, l + 64, ... in w (0 past K).  Each wave then takes whole
+// noise rows, coalesced, and reduces them with DPP (the kernels' own loops: their noise layouts differ).
+template <int NT, int NS>
+__device__ __forceinline__ void dense_weights(const LaneWeight& lw, int k, int K, double* s_e,
+                                              double (&w)[(NS + 63) / 64]) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int k0 = blockIdx.x * NS;
+    if (tid < NS) s_e[tid] = 0.0;
+    __syncthreads();
+    if (lw.nz) s_e[k - k0] = lw.wgt;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < (NS + 63) / 64; ++i) {
+        const int ks = lane + 64 * i;
+        w[i] = (ks < NS && k0 + ks < K) ? s_e[ks] : 0.0;
+    }
+}
+
+// The two-level hand-off merge of the nrows workgroup rows in `slab` (group rows in `gslab`).  Returns
+// (uniformly) whether this workgroup now holds the final merged row in sm; every other workgroup is done.
+// POLL: the rows travel as tagged granules (see st_gran) to consumer workgroups that poll for them — the
+//   first workgroup of each group of kGroup merges its group (the first dispatched are the first done, so
+//   the merger is waiting when the last row lands), workgroup 0 merges the group rows, or every row directly
+//   when few carry weight (direct_merge) — so no workgroup drains its stores or waits on a counter, and the
+//   merges overlap the stragglers.  Needs every workgroup resident at once (the host enables it when the
+//   grid is at most one workgroup per CU); correctness does not depend on placement or order, every value
+//   is tag-checked.  The final merger stores the launch's tag as the new epoch.
+// !POLL: the last workgroup of each group to arrive on its counter merges the group, the last group to
+//   arrive finishes the step, with the same direct_merge decision (identical results either way).
+// direct_dbg: the stamp buffer of direct_merge's own stamps (diagnostic builds; nullptr: none).
+template <int NT, int MAXCH, bool POLL, class SM>
+__device__ __forceinline__ bool handoff_merge(__amdgpu_buffer_rsrc_t slab_r, __amdgpu_buffer_rsrc_t gslab_r, int nrows,
+                                              const RowGeo& geo, double inv_lambda, SM& sm, unsigned* counters,
+                                              bool acquire, unsigned* s_flag, double* partial_out, double* w_eps_out,
+                                              unsigned tag, unsigned* epoch, unsigned* tmo, unsigned long long* dbg,
+                                              unsigned long long* direct_dbg) {
+    const int ngroups = (nrows + kGroup - 1) / kGroup;
+    const int g = blockIdx.x / kGroup;
+    const int gsz = min(kGroup, nrows - g * kGroup);
+    if constexpr (POLL) {
+        // ---- level 1: the group's first workgroup polls and merges its rows
+        if ((int)blockIdx.x != g * kGroup) return false;
+        STAMP(3, NOW());
+        if (ngroups == 1) {
+            merge_rows_block<NT, MAXCH, true, true>(slab_r, 0, gsz, geo, inv_lambda, sm, nullptr, 0, partial_out,
+                                                    w_eps_out, tag, tmo);
+        } else if (blockIdx.x == 0 && nrows <= kDirectRows &&
+                   direct_merge<NT, MAXCH, true>(slab_r, nrows, geo, inv_lambda, sm, partial_out, w_eps_out, tag, tmo,
+                                                 direct_dbg)) {
+            // few weighted rows: finished straight from the workgroup rows
+        } else {
+            merge_rows_block<NT, MAXCH, false, true>(slab_r, g * kGroup, gsz, geo, inv_lambda, sm, &gslab_r, g, nullptr,
+                                                     nullptr, tag, tmo);
+            STAMP(10, NOW());
+            // ---- level 2: workgroup 0 polls and merges the group rows
+            if (blockIdx.x != 0) return false;
+            STAMP(4, NOW());
+            merge_rows_block<NT, MAXCH, true, true>(gslab_r, 0, ngroups, geo, inv_lambda, sm, nullptr, 0, partial_out,
+                                                    w_eps_out, tag, tmo);
+        }
+        // every workgroup read the epoch before publishing, and all have published
+        if (threadIdx.x == 0) __hip_atomic_store(epoch, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        // ---- level 1: the last workgroup of each group of kGroup merges the group
+        if (!arrive_last(counters + g, (unsigned)gsz, s_flag, acquire)) return false;
+        STAMP(3, NOW());
+        merge_rows_block<NT, MAXCH, false, false>(slab_r, g * kGroup, gsz, geo, inv_lambda, sm, &gslab_r, g, nullptr,
+                                                  nullptr, 0u, nullptr);
+        STAMP(10, NOW());
+        // ---- level 2: the last group merges the group rows and finishes the step
+        if (!arrive_last(counters + ngroups, (unsigned)ngroups, s_flag, acquire)) return false;
+        STAMP(4, NOW());
+        if (!(ngroups > 1 && nrows <= kDirectRows &&
+              direct_merge<NT, MAXCH, false>(slab_r, nrows, geo, inv_lambda, sm, partial_out, w_eps_out, 0u, nullptr)))
+            merge_rows_block<NT, MAXCH, true, false>(gslab_r, 0, ngroups, geo, inv_lambda, sm, nullptr, 0, partial_out,
+                                                     w_eps_out, 0u, nullptr);
+    }
+    return true;
+}
+
 // Upper median of 10 (rank 5): a 29-comparator sorting network (verified on all
 // 2^10 0/1 inputs), the element scipy.ndimage.median_filter(size=10) returns.
 __device__ __forceinline__ double median10(double* v) {

@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 
 #include "mppi_device.h"  // XDesc, kSlots, kPadKey, kGroup, kMaxWorld, kTmo*
 #include "mppi_rocm.h"
@@ -49,6 +50,18 @@ inline int launch_check(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MPPI_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
     return MPPI_OK;
+}
+
+// Run-time values as template arguments: f(std::integral_constant<int, V>{}) for the V equal to v (f is not
+// called when there is none), f(std::true_type{}) or f(std::false_type{}) for b.  A context names the kernel
+// instance it uses through these, so each file lists its instantiated kernels once.
+template <int... V, class F>
+void with_value(int v, F&& f) {
+    (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
+}
+template <class F>
+void with_bool(bool b, F&& f) {
+    b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // ------------------------------------------------- launch constants fixed at construction

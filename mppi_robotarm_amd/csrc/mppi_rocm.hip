@@ -312,14 +312,8 @@ __device__ void nominal_update_block(DevStep* nxt, const KConst& c, Scratch& sm,
 
 constexpr int kPF = 4;  // noise rows in flight per lane
 
-// POLL: the partial rows travel as tagged granules (see st_gran) to consumer
-// workgroups that poll for them — the first workgroup of each group of kGroup
-// merges its group, workgroup 0 merges the groups — so no
-// workgroup drains its stores or waits on a counter, and the merges overlap the
-// stragglers.  Needs every workgroup resident at once (the host enables it
-// when the grid is at most one workgroup per CU); correctness does not depend
-// on placement or order, every value is tag-checked.  Otherwise (!POLL) the
-// last workgroup to arrive on a counter merges (arrive_last).
+// POLL: the partial rows travel as polled tagged granules; !POLL: behind arrival counters (handoff_merge in
+// mppi_device.h, which both rollout kernels end with).
 // CLAMP: the sampled controls are clipped to the torque limits (clamp_mode != 0); the CLAMP = false
 // instantiations carry no trace of it.
 template <int LPS, int NT, bool POLL, bool CLAMP>
@@ -515,33 +509,11 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     };
     const double rho_b = block_min_f64<NT>(owner ? S : INFINITY, sm);
     if (tid == 0) publish(blockIdx.x * stride, rho_b);   // the merger's first need, out at once
-    // weights below 2^-64 of the block's best are dropped (see kMergeFloor)
-    // fp64, like the reference's weights; a wave whose samples all lie below the
-    // floor (exp(-44.4) = 2^-64: the usual case, S spread >> lambda) skips the exp
-    const double warg = (rho_b - S) * c.inv_lambda;
-    double wgt = 0.0;
-    if (__any(owner && warg >= -45.0)) wgt = owner ? exp(warg) : 0.0;
-    const bool nz = wgt >= kMergeFloor;
-    const unsigned long long bal = __ballot(nz);
-    const double esum = wave_sum_f64(nz ? wgt : 0.0);
-    if (lane == 0) {
-        s_cnt[wave] = __popcll(bal);
-        s_redd[wave] = esum;
-    }
+    // the epilogue's stages: mppi_device.h, "the rollout epilogue"
+    const LaneWeight lw = block_weigh(owner, S, rho_b, c.inv_lambda, lane, wave, s_cnt, s_redd);
     __syncthreads();
-    int off = 0, nl = 0;
-    double eta_b = 0.0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        off += (w < wave) ? s_cnt[w] : 0;
-        nl += s_cnt[w];
-        eta_b += s_redd[w];
-    }
-    if (nz) {
-        const int pos = off + lanes_below(bal);
-        s_k[pos] = k;
-        s_e[pos] = wgt;
-    }
+    double eta_b;
+    int nl = block_compact<NT>(lw, k, wave, s_cnt, s_redd, s_k, s_e, &eta_b);
     __syncthreads();
     // eta_b leaves next (rho_b left right after the block minimum): a poll merger
     // learns the global minimum and which rows carry weight before the slowest
@@ -566,16 +538,8 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
         constexpr int PER = (NS + 63) / 64;
         constexpr int kRowBatch = 4;
         const int k0 = blockIdx.x * NS;
-        if (tid < NS) s_e[tid] = 0.0;
-        __syncthreads();
-        if (nz) s_e[k - k0] = wgt;
-        __syncthreads();
         double w[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int ks = lane + 64 * i;
-            w[i] = (ks < NS && k0 + ks < K) ? s_e[ks] : 0.0;
-        }
+        dense_weights<NT, NS>(lw, k, K, s_e, w);
         for (int tb = wave * kRowBatch; tb < T; tb += (NT / 64) * kRowBatch) {
             float2 e[kRowBatch][PER];
 #pragma unroll
@@ -604,46 +568,9 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     }
     STAMP(2, NOW());
     STAMP(5, (unsigned long long)nl);
-    const int g = blockIdx.x / kGroup;
-    const int gsz = min(kGroup, nrows - g * kGroup);
-    if constexpr (POLL) {
-        // ---- level 1: the group's first workgroup polls and merges its rows (the first
-        // dispatched are the first done, so the merger is waiting when the last row lands)
-        if ((int)blockIdx.x != g * kGroup) return;
-        STAMP(3, NOW());
-        if (ngroups == 1) {
-            merge_rows_block<NT, 1, true, true>(slab_r, 0, gsz, geo, c.inv_lambda, sm, nullptr, 0, partial_out, w_eps_out, tag, tmo);
-        } else if (blockIdx.x == 0 && nrows <= kDirectRows &&
-                   direct_merge<NT, 1, true>(slab_r, nrows, geo, c.inv_lambda, sm, partial_out, w_eps_out, tag, tmo, dbg)) {
-            // few weighted rows: finished straight from the workgroup rows
-        } else {
-            merge_rows_block<NT, 1, false, true>(slab_r, g * kGroup, gsz, geo, c.inv_lambda, sm, &gslab_r, g, nullptr, nullptr, tag,
-                                                 tmo);
-            STAMP(10, NOW());
-            // ---- level 2: workgroup 0 polls and merges the group rows
-            if (blockIdx.x != 0) return;
-            STAMP(4, NOW());
-            merge_rows_block<NT, 1, true, true>(gslab_r, 0, ngroups, geo, c.inv_lambda, sm, nullptr, 0, partial_out,
-                                                w_eps_out, tag, tmo);
-        }
-        // every workgroup read the epoch before publishing, and all have published
-        if (threadIdx.x == 0) __hip_atomic_store(epoch, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        // ---- level 1: the last workgroup of each group of kGroup merges the group
-        if (!arrive_last(counters + g, (unsigned)gsz, &s_flag, c.acquire != 0)) return;
-        STAMP(3, NOW());
-        merge_rows_block<NT, 1, false, false>(slab_r, g * kGroup, gsz, geo, c.inv_lambda, sm, &gslab_r, g, nullptr, nullptr,
-                                              0u, nullptr);
-        STAMP(10, NOW());
-        // ---- level 2: the last group merges the group rows and finishes the step
-        if (!arrive_last(counters + ngroups, (unsigned)ngroups, &s_flag, c.acquire != 0)) return;
-        STAMP(4, NOW());
-        // the same decision as the poll form (identical results either way)
-        if (!(ngroups > 1 && nrows <= kDirectRows &&
-              direct_merge<NT, 1, false>(slab_r, nrows, geo, c.inv_lambda, sm, partial_out, w_eps_out, 0u, nullptr)))
-            merge_rows_block<NT, 1, true, false>(gslab_r, 0, ngroups, geo, c.inv_lambda, sm, nullptr, 0, partial_out,
-                                                 w_eps_out, 0u, nullptr);
-    }
+    if (!handoff_merge<NT, 1, POLL>(slab_r, gslab_r, nrows, geo, c.inv_lambda, sm, counters, c.acquire != 0, &s_flag,
+                                    partial_out, w_eps_out, tag, epoch, tmo, dbg, dbg))
+        return;
     STAMP(11, NOW());
     STAMP(6, (unsigned long long)sm.nrel);
     if (flags & MPPI_FLAG_EXCHANGE) {
@@ -855,11 +782,27 @@ namespace {
 using mppi_host::fail;
 using mppi_host::launch_check;
 
-// of the kernel the context will launch: the CLAMP form holds two more register pairs
-template <int L, int N>
-int occupancy(int* per_cu, bool clamp) {
-    const void* f = clamp ? (const void*)rollout_kernel<L, N, true, true> : (const void*)rollout_kernel<L, N, true, false>;
-    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, N, 0);
+using mppi_host::with_bool;
+using mppi_host::with_value;
+
+// The instantiated rollout kernels: LPS in {1, 2, 4, 8, 16} x NT in {256, 512} x POLL x CLAMP.  Calls
+// f(lps, nt, poll, clamp), the context's instance as integral constants, in the hand-off form `poll`.
+template <class F>
+void with_rollout(const mppi_ctx* c, bool poll, F&& f) {
+    with_value<1, 2, 4, 8, 16>(c->lps, [&](auto lps) {
+        with_value<256, 512>(c->nt, [&](auto nt) {
+            with_bool(poll, [&](auto p) { with_bool(c->ck.mode != 0, [&](auto cl) { f(lps, nt, p, cl); }); });
+        });
+    });
+}
+
+// After a launch (rc: its launch_check): a fused update made the other ping-pong block current.  True if so.
+bool took_update(mppi_ctx* c, int rc, unsigned flags) {
+    if (rc != MPPI_OK || !(flags & MPPI_FLAG_FUSED_UPDATE)) return false;
+    c->cur ^= 1;
+    c->upd_valid = true;
+    c->nominal_published = false;   // until wait_host_out sees this launch's outputs
+    return true;
 }
 
 int check_timeout(mppi_ctx* c) {
@@ -902,20 +845,11 @@ int alloc(mppi_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     int ncu = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-    {
-        const int lps = c->lps;
-        const bool cl = c->ck.mode != 0;
-        int rc = 0;
-        if (c->nt == 512)
-            rc = lps == 1 ? occupancy<1, 512>(&per_cu, cl) : lps == 2 ? occupancy<2, 512>(&per_cu, cl)
-               : lps == 4 ? occupancy<4, 512>(&per_cu, cl) : lps == 8 ? occupancy<8, 512>(&per_cu, cl)
-               : occupancy<16, 512>(&per_cu, cl);
-        else
-            rc = lps == 1 ? occupancy<1, 256>(&per_cu, cl) : lps == 2 ? occupancy<2, 256>(&per_cu, cl)
-               : lps == 4 ? occupancy<4, 256>(&per_cu, cl) : lps == 8 ? occupancy<8, 256>(&per_cu, cl)
-               : occupancy<16, 256>(&per_cu, cl);
-        if (rc != 0) per_cu = 0;
-    }
+    // of the kernel the context will launch (the CLAMP form holds two more register pairs), always its POLL form
+    with_rollout(c, true, [&](auto lps, auto nt, auto p, auto cl) {
+        const void* f = (const void*)rollout_kernel<lps, nt, p, cl>;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, nt, 0) != hipSuccess) per_cu = 0;
+    });
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + 2 * c->cfg.T, 0)) return rc;
     c->kc.acquire = c->hand.acquire;
     HIP_TRY(hipMalloc(&c->d_step, 2 * sizeof(DevStep)));
@@ -1203,44 +1137,14 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
     const DevStep* cur = c->d_step + c->cur;
     DevStep* nxt = c->d_step + (c->cur ^ 1);
     const float2* nz = reinterpret_cast<const float2*>(noise_dev);
-#define MPPI_LAUNCH(L, NTH, P, CL)                                                                               \
-    hipLaunchKernelGGL((rollout_kernel<L, NTH, P, CL>), dim3(c->nblocks), dim3(NTH), 0, c->stream, c->kc, c->stat, cur, nz, \
-                       S_dev, c->hand.d_slab, c->hand.d_gslab, c->hand.d_counter, partial_dev, c->d_weps, nxt, flags,  \
-                       c->ex.xd, c->hand.d_epoch, c->hand.d_tmo, reinterpret_cast<float*>(c->d_upd), ho, c->d_dbg, \
-                       c->ck)
-#define MPPI_LAUNCH_C(L, NTH, P)                            \
-    do {                                                    \
-        if (c->ck.mode != 0) MPPI_LAUNCH(L, NTH, P, true);  \
-        else MPPI_LAUNCH(L, NTH, P, false);                 \
-    } while (0)
-#define MPPI_LAUNCH_P(L, NTH)                \
-    do {                                     \
-        if (c->hand.poll) MPPI_LAUNCH_C(L, NTH, true);  \
-        else MPPI_LAUNCH_C(L, NTH, false);   \
-    } while (0)
-    if (c->nt == 512) {
-        if (c->lps == 1) MPPI_LAUNCH_P(1, 512);
-        else if (c->lps == 2) MPPI_LAUNCH_P(2, 512);
-        else if (c->lps == 4) MPPI_LAUNCH_P(4, 512);
-        else if (c->lps == 8) MPPI_LAUNCH_P(8, 512);
-        else MPPI_LAUNCH_P(16, 512);
-    } else {
-        if (c->lps == 1) MPPI_LAUNCH_P(1, 256);
-        else if (c->lps == 2) MPPI_LAUNCH_P(2, 256);
-        else if (c->lps == 4) MPPI_LAUNCH_P(4, 256);
-        else if (c->lps == 8) MPPI_LAUNCH_P(8, 256);
-        else MPPI_LAUNCH_P(16, 256);
-    }
-#undef MPPI_LAUNCH_P
-#undef MPPI_LAUNCH_C
-#undef MPPI_LAUNCH
+    with_rollout(c, c->hand.poll, [&](auto lps, auto nt, auto p, auto cl) {
+        hipLaunchKernelGGL((rollout_kernel<lps, nt, p, cl>), dim3(c->nblocks), dim3(nt), 0, c->stream, c->kc, c->stat, cur,
+                           nz, S_dev, c->hand.d_slab, c->hand.d_gslab, c->hand.d_counter, partial_dev, c->d_weps, nxt,
+                           flags, c->ex.xd, c->hand.d_epoch, c->hand.d_tmo, reinterpret_cast<float*>(c->d_upd), ho,
+                           c->d_dbg, c->ck);
+    });
     const int rc = launch_check("rollout_kernel");
-    if (rc == MPPI_OK && (flags & MPPI_FLAG_FUSED_UPDATE)) {
-        c->cur ^= 1;
-        c->upd_valid = true;
-        c->nominal_published = false;   // until wait_host_out sees this launch's outputs
-        c->x_flipped = (flags & MPPI_FLAG_EXCHANGE) != 0;   // undone if the exchange fails (check_timeout)
-    }
+    if (took_update(c, rc, flags)) c->x_flipped = (flags & MPPI_FLAG_EXCHANGE) != 0;   // undone if the exchange fails
     return rc;
 }
 }  // namespace
@@ -1274,11 +1178,7 @@ int mppi_merge_partials(mppi_ctx* c, const double* partials_dev, int n, unsigned
     hipLaunchKernelGGL(f, dim3(1), dim3(big ? 512 : 256), 0, c->stream, c->kc, partials_dev, n, c->d_weps, cur, nxt,
                        flags, reinterpret_cast<float*>(c->d_upd), ho, c->ck);
     const int rc = launch_check("merge_kernel");
-    if (rc == MPPI_OK && (flags & MPPI_FLAG_FUSED_UPDATE)) {
-        c->cur ^= 1;
-        c->upd_valid = true;
-        c->nominal_published = false;   // until wait_host_out sees this launch's outputs
-    }
+    took_update(c, rc, flags);
     return rc;
 }
 

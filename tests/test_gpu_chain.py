@@ -177,6 +177,41 @@ def test_chain_handoff_forms_are_bit_identical(lam, lps, paths, monkeypatch):
         assert np.array_equal(wp, wc) and np.array_equal(up, uc)
 
 
+@pytest.mark.parametrize("K,lps,lam", [(4352, 1, 100.0), (4352, 1, 1.0e9), (1088, 4, 100.0), (1088, 4, 1.0e9),
+                                       (1024, 1, 100.0), (1024, 1, 1.0e9)])
+def test_chain_handoff_small_grids_both_forms(K, lps, lam, paths, monkeypatch):
+    """The hand-off's branches at the smallest grids that reach them, on the odd chain with a pad link (n = 3,
+    T = 5): 17 workgroups (two merge groups; one-hot weights at lambda = 100 take the sparse gather and the
+    direct merge, every sample weighted at 1e9 takes the dense gather, 17 weighted rows are more than the direct
+    merge takes, and the merge goes through the group rows) at one lane per sample and at four, and 4 workgroups
+    (one group).  Both forms give the same bits over four fused launches, and the first launch's weighted noise
+    is the fp64 oracle's."""
+    from mppi_robotarm_amd.chain import ChainEngine
+    n, T = 3, 5
+    P, Po, x0, sig, u = _link_inputs(n, T)
+    win = paths["xydq_circle"][40:70]
+    runs = {}
+    for form in ("poll", "counter"):
+        if form == "counter":
+            monkeypatch.setenv("MPPI_HANDOFF", "counter")
+        eng = ChainEngine(K, T, 0.006, lam, 0.98, sig, W, TW, 0.0, P, device=0, lanes_per_sample=lps)
+        assert eng.handoff == form and eng.lanes_per_sample == lps
+        noises = [eng.philox_noise(17, s) for s in range(4)]
+        eng.set_step_inputs(x0, win, u)
+        out = []
+        for nz in noises:
+            eng.rollout(nz, fused_update=True)
+            out.append((eng.weighted_noise(), eng.nominal()))
+        runs[form] = out
+        nz0 = noises[0].cpu().numpy().transpose(0, 2, 1)   # device [T][K][n] -> (T, n, K)
+        eng.close()
+    for (wp, up), (wc, uc) in zip(runs["poll"], runs["counter"]):
+        assert np.array_equal(wp, wc) and np.array_equal(up, uc)
+    Sr = coracle.chain_rollout_costs(x0, u, nz0, win, 0.006, lam, 0.98, sig, W, TW, Po, layout="TNK")
+    _, wr = coracle.chain_weighted_noise(Sr, nz0, lam, layout="TNK")
+    assert _urel(runs["poll"][0][0], wr) < U_TOL
+
+
 @pytest.mark.parametrize("precision,lps", [("f32", 1), ("f32", 4), ("f64", 1)])
 def test_chain_fused_update_matches_host_update(precision, lps, paths):
     from scipy.ndimage import median_filter
@@ -283,10 +318,10 @@ def _uniform_chain(mod, n):
                            J=(0.1,) * n, b=(1.0,) * n)
 
 
-def _link_case(n, K, T, lam, paths, precision="f32", lps=1):
-    """A uniform n-link chain with a random SPD Sigma, gravity-holding nominal plus noise and a window away from
-    the path start, through the engine and the C fp64 chain oracle: (S, S_ref, w_eps, w_eps_ref, tie inputs)."""
-    from mppi_robotarm_amd.chain import ChainEngine, ChainParams, gravity_torque
+def _link_inputs(n, T):
+    """A uniform n-link chain (the engine's parameters and the oracle's), a start state, a random SPD Sigma and a
+    gravity-holding nominal plus noise."""
+    from mppi_robotarm_amd.chain import ChainParams, gravity_torque
     rng = np.random.default_rng(n * 100 + T)
     import mppi_robotarm_amd.chain as chain_mod
     P, Po = _uniform_chain(chain_mod, n), _uniform_chain(CO, n)
@@ -296,6 +331,14 @@ def _link_case(n, K, T, lam, paths, precision="f32", lps=1):
     A = rng.normal(0, 1, (n, n))
     sig = A @ A.T / n + np.diag(np.linspace(8.0, 1.0, n))
     u = np.tile(gravity_torque(q, P), (T, 1)) + rng.normal(0, 0.3, (T, n))
+    return P, Po, x0, sig, u
+
+
+def _link_case(n, K, T, lam, paths, precision="f32", lps=1):
+    """The chain of _link_inputs and a window away from the path start, through the engine and the C fp64
+    chain oracle: (S, S_ref, w_eps, w_eps_ref, tie inputs)."""
+    from mppi_robotarm_amd.chain import ChainEngine
+    P, Po, x0, sig, u = _link_inputs(n, T)
     eng = ChainEngine(K, T, 0.006, lam, 0.98, sig, W, TW, 0.0, P, device=0, precision=precision,
                       lanes_per_sample=lps)
     win = paths["xydq_circle"][40:70]

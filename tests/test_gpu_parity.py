@@ -179,6 +179,37 @@ def test_handoff_forms_are_bit_identical(lam, paths, monkeypatch):
         assert np.array_equal(up, uc)
 
 
+@pytest.mark.parametrize("K,lam", [(4352, 100.0), (4352, 1.0e9), (1024, 100.0), (1024, 1.0e9), (16640, 1.0e9)])
+def test_handoff_small_grids_both_forms(K, lam, paths, monkeypatch):
+    """The hand-off's remaining branches at the smallest grids that reach them, one lane per sample: 17
+    workgroups of 256 (two merge groups, finished by the direct merge: at T = 8 a row has 17 columns, so it
+    spreads up to 64 weighted rows over its row groups) and 4 (one group, merged by its own merger), with
+    one-hot weights (lambda = 100, the sparse gather) and with every sample weighted (1e9, the dense gather);
+    65 workgroups, all weighted, are one row more than the direct merge takes: the two-level merge.
+    Both forms give the same bits over four fused launches, and the first launch's weighted noise is the fp64
+    oracle's."""
+    T = 8
+    runs = {}
+    for form in ("poll", "counter"):
+        if form == "counter":
+            monkeypatch.setenv("MPPI_HANDOFF", "counter")
+        eng = _engine(K, T, lps=1, param_lambda=lam)
+        assert eng.handoff == form and eng.blocks == (K + 255) // 256
+        noises = [eng.philox_noise(13, s) for s in range(4)]
+        runs[form] = _fused_steps(eng, paths, noises, T)
+        eps_tk = noises[0].cpu().numpy()
+        eng.synchronize()
+        eng.close()
+    for (wp, up), (wc, uc) in zip(runs["poll"], runs["counter"]):
+        assert np.array_equal(wp, wc)
+        assert np.array_equal(up, uc)
+    ref_S = coracle.rollout_costs(X0, np.array([[10.0, -2.0]] * T), eps_tk, _window(paths, 3), 0.006, lam, 0.98,
+                                  np.eye(2) * 20.0, RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"],
+                                  O.ArmParams(), layout="TK")
+    _, ref_weps = coracle.weighted_noise(ref_S, eps_tk, lam, layout="TK")
+    assert _urel(runs["poll"][0][0], ref_weps) < U_TOL
+
+
 def test_graph_replay_matches_eager(paths):
     """HIP-graph replay of fused launches (frozen kernel arguments; the granule
     epoch lives in device memory) == the same launches issued eagerly.  An even
