@@ -1270,22 +1270,23 @@ struct mppi_chain_ctx {
     int nblocks = 0;
     mppi_host::Handoff hand;       // hand-off form, its buffers and the time-out words
     ChainConst kc;
-    ChainStep* d_step = nullptr;   // [2] ping-pong
+    mppi_host::DevBuf<ChainStep> d_step;      // [2] ping-pong
     int cur = 0;
-    ChainStep* h_step = nullptr;   // pinned staging
-    hipEvent_t staged = nullptr;
-    unsigned long long* d_runmin = nullptr;   // running minimum of the workgroups' rho_b (ord_key), ~0 between launches
-    double* d_weps = nullptr;
-    double* h_buf = nullptr;
-    float* d_base = nullptr;
-    float* h_base = nullptr;
+    mppi_host::PinnedBuf<ChainStep> h_step;   // pinned staging
+    mppi_host::Event staged;
+    // running minimum of the workgroups' rho_b (ord_key), ~0 between launches
+    mppi_host::DevBuf<unsigned long long> d_runmin;
+    mppi_host::DevBuf<double> d_weps;
+    mppi_host::PinnedBuf<double> h_buf;
+    mppi_host::DevBuf<float> d_base;
+    mppi_host::PinnedBuf<float> h_base;
     CholArg chol{};                // Cholesky factor of Sigma x kBoxMullerScale (kCMax x kCMax, fp32) for the Philox noise
-    float* d_dyn = nullptr;        // packed per-step constants (DynMem), then the same in fp64 at kDynF64Off
+    mppi_host::DevBuf<float> d_dyn;   // packed per-step constants (DynMem), then the same in fp64 at kDynF64Off
     double h_dynd[kCDyn] = {};     // the fp64 constants on the host (the optimal trajectory)
     bool upd_valid = false;        // the current step block holds a fused update's output
     bool pub_valid = false;        // ... and h_pub is its shifted nominal as mppi_chain_wait_outputs returned it
-    double* h_out = nullptr;       // MPPI_FLAG_HOST_OUT: the update's read-back, queued right behind the launch
-    hipEvent_t out_ev = nullptr;   // ... recorded after that copy
+    mppi_host::PinnedBuf<double> h_out;   // MPPI_FLAG_HOST_OUT: the update's read-back, queued right behind the launch
+    mppi_host::Event out_ev;       // ... recorded after that copy
     bool out_posted = false;
     bool x_flipped = false;        // the last launch flipped the ping-pong and exchanged (undone on MPPI_E_EXCHANGE)
     double last_eta = NAN;         // the weights' spread of the last update / weighted noise read back
@@ -1309,12 +1310,13 @@ void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise,
         if constexpr (N == kCDebugN)
             hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, true>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc,
                                cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags,
-                               c->ex.xd, h.d_epoch, h.d_tmo, c->d_runmin, reinterpret_cast<unsigned long long*>(slots));
+                               c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin,
+                               reinterpret_cast<unsigned long long*>(slots));
         return;
     }
     hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc, cur, c->d_dyn,
-                       noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags, c->ex.xd, h.d_epoch, h.d_tmo,
-                       c->d_runmin, c->d_dbg);
+                       noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags, c->ex.xd, h.d_epoch,
+                       h.h_tmo.dev, c->d_runmin, c->d_dbg);
 }
 
 // the link counts with an instantiated kernel: f(N) for N = n as an integral constant
@@ -1383,7 +1385,7 @@ int check_tmo(mppi_chain_ctx* c) {
 }
 
 // The device side of mppi_chain_ctx_create: the hand-off form from the rollout kernel's occupancy, then
-// every buffer (on an error the caller destroys the half-built context).
+// every buffer (on an error the caller deletes the half-built context, whose members free what they hold).
 int alloc(mppi_chain_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     int ncu = 0, per_cu = 0;
@@ -1396,22 +1398,20 @@ int alloc(mppi_chain_ctx* c) {
     c->kc.acquire = c->hand.acquire;
     c->kc.cu_off = (int)c->hand.extra_off;
     c->kc.fair = c->nblocks > ncu ? 1 : 0;
-    HIP_TRY(hipMalloc(&c->d_step, 2 * sizeof(ChainStep)));
-    HIP_TRY(hipMalloc(&c->d_runmin, 256));
+    if (int rc = c->d_step.alloc_zeroed(2)) return rc;
+    if (int rc = c->d_runmin.alloc(256 / sizeof(unsigned long long))) return rc;
     HIP_TRY(hipMemset(c->d_runmin, 0xFF, 256));
-    HIP_TRY(hipMalloc(&c->d_weps, (kCMaxVals + 1) * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->d_base, kCMaxVals * sizeof(float)));
-    HIP_TRY(hipMalloc(&c->d_dyn, kDynF64Off * sizeof(float) + sizeof(c->h_dynd)));
+    if (int rc = c->d_weps.alloc_zeroed(kCMaxVals + 1)) return rc;
+    if (int rc = c->d_base.alloc(kCMaxVals)) return rc;
+    if (int rc = c->d_dyn.alloc(kDynF64Off + 2 * kCDyn)) return rc;   // the fp32 table, then h_dynd
     HIP_TRY(hipMemcpy(c->d_dyn + kDynF64Off, c->h_dynd, sizeof(c->h_dynd), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_dyn, c->kc.dyn, sizeof(c->kc.dyn), hipMemcpyHostToDevice));
-    HIP_TRY(hipHostMalloc(&c->h_step, sizeof(ChainStep), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&c->h_buf, (kCMaxVals + kCMax) * sizeof(double), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&c->h_base, kCMaxVals * sizeof(float), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&c->h_out, (kCMaxVals + kCMax + 1) * sizeof(double), hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&c->staged, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->out_ev, hipEventDisableTiming));
-    HIP_TRY(hipMemset(c->d_step, 0, 2 * sizeof(ChainStep)));
-    HIP_TRY(hipMemset(c->d_weps, 0, (kCMaxVals + 1) * sizeof(double)));
+    if (int rc = c->h_step.alloc(1)) return rc;
+    if (int rc = c->h_buf.alloc(kCMaxVals + kCMax)) return rc;
+    if (int rc = c->h_base.alloc(kCMaxVals)) return rc;
+    if (int rc = c->h_out.alloc(kCMaxVals + kCMax + 1)) return rc;
+    if (int rc = c->staged.create()) return rc;
+    if (int rc = c->out_ev.create()) return rc;
     HIP_TRY(hipDeviceSynchronize());
     memset(c->h_step, 0, sizeof(ChainStep));
     return MPPI_OK;
@@ -1468,26 +1468,18 @@ int mppi_chain_ctx_create(const mppi_chain_config* cfg, int device, void* stream
             for (int i = 0; i < n; ++i) Si[i * n + col] = y[i];
         }
     }
-    mppi_chain_ctx* c = new mppi_chain_ctx();
+    auto c = std::make_unique<mppi_chain_ctx>();
     c->cfg = *cfg;
     c->device = device;
     c->n = n;
     c->stream = (hipStream_t)stream;
     c->f64 = cfg->precision == 1;
     c->lps = cfg->lanes_per_sample > 0 ? cfg->lanes_per_sample : chain_auto_lps(cfg->K_local, c->f64);
-    if (c->lps != 1 && c->lps != 4) {
-        delete c;
-        return fail(MPPI_E_ARG, "lanes_per_sample must be 0 (auto), 1 or 4");
-    }
-    if (c->lps == 4 && c->f64) {
-        delete c;
-        return fail(MPPI_E_ARG, "lanes_per_sample 4 is for the fp32 rollout");
-    }
+    if (c->lps != 1 && c->lps != 4) return fail(MPPI_E_ARG, "lanes_per_sample must be 0 (auto), 1 or 4");
+    if (c->lps == 4 && c->f64) return fail(MPPI_E_ARG, "lanes_per_sample 4 is for the fp32 rollout");
     if (c->lps == 4 && (long long)cfg->K_local * cfg->T * n * 4 >= (1LL << 31)) {   // its noise buffer offsets
-        if (cfg->lanes_per_sample > 0) {
-            delete c;
+        if (cfg->lanes_per_sample > 0)
             return fail(MPPI_E_ARG, "lanes_per_sample 4 needs K_local * T * n * 4 below 2^31 bytes of noise");
-        }
         c->lps = 1;
     }
     c->nblocks = (int)(((long long)cfg->K_local * c->lps + kCT - 1) / kCT);
@@ -1522,11 +1514,8 @@ int mppi_chain_ctx_create(const mppi_chain_config* cfg, int device, void* stream
 
     for (int i = 0; i < n; ++i)
         for (int j = 0; j <= i; ++j) c->chol.L[i * kCMax + j] = (float)(Lc[i][j] * kBoxMullerScale);   // box_muller's constant
-    if (int rc = alloc(c)) {
-        mppi_chain_ctx_destroy(c);
-        return rc;
-    }
-    *out = c;
+    if (int rc = alloc(c.get())) return rc;
+    *out = c.release();
     return MPPI_OK;
 }
 
@@ -1534,19 +1523,6 @@ void mppi_chain_ctx_destroy(mppi_chain_ctx* c) {
     if (!c) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipDeviceSynchronize();
-    (void)hipFree(c->d_step);
-    c->hand.release();
-    (void)hipFree(c->d_runmin);
-    (void)hipFree(c->d_weps);
-    (void)hipFree(c->d_base);
-    (void)hipFree(c->d_dyn);
-    c->ex.release();
-    if (c->h_step) (void)hipHostFree(c->h_step);
-    if (c->h_buf) (void)hipHostFree(c->h_buf);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->out_ev) (void)hipEventDestroy(c->out_ev);
-    if (c->h_base) (void)hipHostFree(c->h_base);
-    if (c->staged) (void)hipEventDestroy(c->staged);
     delete c;
 }
 

@@ -1,5 +1,6 @@
 // mppi_host.h — the host-side plumbing shared by the translation units of
 // libmppi_rocm.so: the one error channel behind mppi_last_error(), HIP_TRY,
+// the owners of every HIP buffer, event and stream the four contexts hold,
 // and what the 2-link context (mppi_rocm.hip) and the chain's (mppi_chain.hip)
 // both carry: the launch constants fixed at construction, the staging of the
 // waypoint window, the in-launch hand-off's buffers and time-out verdict, and
@@ -14,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <type_traits>
 
@@ -51,6 +53,93 @@ inline int launch_check(const char* what) {
     if (e != hipSuccess) return fail(MPPI_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
     return MPPI_OK;
 }
+
+// ------------------------------------------------- owners of HIP resources
+//
+// What a context allocates is a member of one of these: the destructor releases it, so a half-built context and
+// a destroyed one end the same way and no *_destroy lists buffers.  Not copyable and not movable (the contexts
+// are heap objects that never move); each converts to its raw pointer or handle, so launches and copies read as
+// with raw members.  What can fail returns a code through HIP_TRY and leaves the owner empty; n counts elements.
+template <class H, auto Drop>
+struct Owner {
+    H h = nullptr;
+    Owner() = default;
+    Owner(const Owner&) = delete;
+    Owner& operator=(const Owner&) = delete;
+    ~Owner() { reset(); }
+    operator H() const { return h; }
+    void reset() {
+        if (h) (void)Drop(h);
+        h = nullptr;
+    }
+};
+
+template <class T>
+struct DevBuf : Owner<T*, hipFree> {
+    size_t cap = 0;
+    void reset(T* block = nullptr, size_t n = 0) {   // frees; with a block, takes it over (Exchange's uncached inbox)
+        Owner<T*, hipFree>::reset();
+        this->h = block;
+        cap = n;
+    }
+    int alloc(size_t n) {
+        reset();
+        HIP_TRY(hipMalloc(&this->h, n * sizeof(T)));
+        cap = n;
+        return MPPI_OK;
+    }
+    int alloc_zeroed(size_t n) {
+        if (int rc = alloc(n)) return rc;
+        HIP_TRY(hipMemset(this->h, 0, n * sizeof(T)));
+        return MPPI_OK;
+    }
+    // At least n elements: untouched while cap suffices, else freed first and allocated anew (contents are not
+    // carried over), which *fresh = true reports.
+    int reserve(size_t n, bool* fresh) {
+        if (n <= cap) return MPPI_OK;
+        *fresh = true;
+        return alloc(n);
+    }
+};
+
+template <class T>
+struct PinnedBuf : Owner<T*, hipHostFree> {
+    T* operator->() const { return this->h; }
+    int alloc(size_t n, unsigned flags = hipHostMallocDefault) {
+        this->reset();
+        HIP_TRY(hipHostMalloc(&this->h, n * sizeof(T), flags));
+        return MPPI_OK;
+    }
+};
+
+constexpr unsigned kCoherent = hipHostMallocCoherent;   // MappedBuf::alloc's flag
+template <class T>
+struct MappedBuf : PinnedBuf<T> {   // host-mapped: converts to the host pointer, dev is its device view
+    T* dev = nullptr;
+    void reset() { PinnedBuf<T>::reset(), dev = nullptr; }
+    int alloc(size_t n, unsigned flags) {   // flags: 0 or kCoherent
+        reset();
+        if (int rc = PinnedBuf<T>::alloc(n, hipHostMallocMapped | flags)) return rc;
+        HIP_TRY(hipHostGetDevicePointer((void**)&dev, this->h, 0));
+        return MPPI_OK;
+    }
+};
+
+struct Event : Owner<hipEvent_t, hipEventDestroy> {
+    int create() {
+        reset();
+        HIP_TRY(hipEventCreateWithFlags(&h, hipEventDisableTiming));
+        return MPPI_OK;
+    }
+};
+
+struct Stream : Owner<hipStream_t, hipStreamDestroy> {
+    int create() {
+        reset();
+        HIP_TRY(hipStreamCreateWithFlags(&h, hipStreamNonBlocking));
+        return MPPI_OK;
+    }
+};
 
 // Run-time values as template arguments: f(std::integral_constant<int, V>{}) for the V equal to v (f is not
 // called when there is none), f(std::true_type{}) or f(std::false_type{}) for b.  A context names the kernel
@@ -157,12 +246,10 @@ struct Handoff {
     size_t slab = 0, gslab = 0;     // bytes of the workgroup rows and of the group rows
     size_t extra_off = 0;           // word offset of the caller's extra words in the counter block (256-B aligned)
     size_t ctr_bytes = 0;
-    double* d_slab = nullptr;
-    double* d_gslab = nullptr;
-    unsigned* d_counter = nullptr;  // [ngroups + 1] arrival counters (counter hand-off), then the epoch word
+    DevBuf<double> d_slab, d_gslab;
+    DevBuf<unsigned> d_counter;     // [ngroups + 1] arrival counters (counter hand-off), then the epoch word
     unsigned* d_epoch = nullptr;    // granule epoch (poll hand-off), inside the d_counter block
-    unsigned* h_tmo = nullptr;      // host-mapped: a bounded in-launch spin gave up
-    unsigned* d_tmo = nullptr;
+    MappedBuf<unsigned> h_tmo;      // host-mapped: a bounded in-launch spin gave up
 
     // Form and sizes (no HIP call).  per_cu: the rollout kernel's occupancy (0: not known); stride: values of
     // a partial row; extra_words: counter words of the caller's own behind the block.
@@ -182,23 +269,13 @@ struct Handoff {
     // plan(), then the buffers, zeroed (the caller synchronizes the device before the first launch).
     int setup(int nblocks, int ncu, int per_cu, int stride, size_t extra_words) {
         plan(nblocks, ncu, per_cu, stride, extra_words);
-        HIP_TRY(hipMalloc(&d_slab, slab));
-        HIP_TRY(hipMalloc(&d_gslab, gslab));
-        HIP_TRY(hipMalloc(&d_counter, ctr_bytes));
-        HIP_TRY(hipHostMalloc(&h_tmo, 256, hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer((void**)&d_tmo, h_tmo, 0));
-        HIP_TRY(hipMemset(d_counter, 0, ctr_bytes));
-        HIP_TRY(hipMemset(d_slab, 0, slab));
-        HIP_TRY(hipMemset(d_gslab, 0, gslab));
+        if (int rc = d_slab.alloc_zeroed(slab / sizeof(double))) return rc;
+        if (int rc = d_gslab.alloc_zeroed(gslab / sizeof(double))) return rc;
+        if (int rc = d_counter.alloc_zeroed(ctr_bytes / sizeof(unsigned))) return rc;
+        if (int rc = h_tmo.alloc(256 / sizeof(unsigned), 0)) return rc;
         h_tmo[0] = h_tmo[1] = 0;
         d_epoch = d_counter + ngroups + 1;
         return MPPI_OK;
-    }
-    void release() {
-        (void)hipFree(d_slab);
-        (void)hipFree(d_gslab);
-        (void)hipFree(d_counter);
-        if (h_tmo) (void)hipHostFree(h_tmo);
     }
     int take_timeout(unsigned* bits) { return mppi_host::take_timeout(h_tmo, bits); }
 };
@@ -208,11 +285,16 @@ struct Handoff {
 // The inbox, this rank's row, its epoch and the peers' mappings behind the kernels' XDesc.
 struct Exchange {
     mppi::XDesc xd{};
-    void* d_inbox = nullptr;
-    double* d_xrow = nullptr;
-    unsigned* d_xepoch = nullptr;
+    DevBuf<char> d_inbox;           // hipDeviceMallocUncached
+    DevBuf<double> d_xrow;
+    DevBuf<unsigned> d_xepoch;
     int world_alloc = 0;
     void* opened[mppi::kMaxWorld] = {};
+
+    ~Exchange() {   // the peers' mappings close before the members free the inbox
+        for (void* p : opened)
+            if (p) (void)hipIpcCloseMemHandle(p);
+    }
 
     // Allocates the inbox for `world` ranks' rows of `stride` values on first use; its IPC handle.
     int handle(int device, int stride, int world, void* handle_out) {
@@ -220,11 +302,12 @@ struct Exchange {
         if (!d_inbox) {
             const size_t bytes = (size_t)2 * world * (stride + 1) * 16;   // rows and statuses, two parities
             HIP_TRY(hipSetDevice(device));
-            HIP_TRY(hipExtMallocWithFlags(&d_inbox, bytes, hipDeviceMallocUncached));
+            void* inbox = nullptr;
+            HIP_TRY(hipExtMallocWithFlags(&inbox, bytes, hipDeviceMallocUncached));
+            d_inbox.reset(static_cast<char*>(inbox), bytes);
             HIP_TRY(hipMemset(d_inbox, 0, bytes));
-            HIP_TRY(hipMalloc(&d_xrow, stride * sizeof(double)));
-            HIP_TRY(hipMalloc(&d_xepoch, 256));
-            HIP_TRY(hipMemset(d_xepoch, 0, 256));
+            if (int rc = d_xrow.alloc(stride)) return rc;
+            if (int rc = d_xepoch.alloc_zeroed(256 / sizeof(unsigned))) return rc;
             HIP_TRY(hipDeviceSynchronize());
             world_alloc = world;
             xd.bytes = (int)bytes;
@@ -253,13 +336,6 @@ struct Exchange {
         xd.world = world;
         xd.timeout_ticks = exchange_timeout_ticks();
         return MPPI_OK;
-    }
-    void release() {
-        for (void* p : opened)
-            if (p) (void)hipIpcCloseMemHandle(p);
-        (void)hipFree(d_inbox);
-        (void)hipFree(d_xrow);
-        (void)hipFree(d_xepoch);
     }
 };
 

@@ -503,25 +503,22 @@ __global__ __launch_bounds__(kNT) void np_state_kernel(const uint32_t* __restric
 
 struct mppi_np_ctx {
     int device = 0;
-    double* d_log = nullptr;
-    uint32_t* d_seq = nullptr;      // kSeqBlocks blocks
+    mppi_host::DevBuf<double> d_log;
+    mppi_host::DevBuf<uint32_t> d_seq;      // kSeqBlocks blocks
     int poly_P = 0, poly_streams = 0;
-    uint32_t* d_nibs = nullptr;     // table jump: the polynomials' 4-bit chunks, [chunk][group][jump], one per word
+    // table jump: the polynomials' 4-bit chunks, [chunk][group][jump], one per word
+    mppi_host::DevBuf<uint32_t> d_nibs;
     int jG = 0, jR = 0, jcpw = 0;   // table jump: stream groups, chunk ranges, chunks per range
     int jparts = 1;                 // partial XORs per stream that np_gen_kernel combines
-    uint32_t* d_jumped = nullptr;
-    uint32_t* d_words = nullptr;
-    size_t words_cap = 0;           // words
+    mppi_host::DevBuf<uint32_t> d_jumped;
+    mppi_host::DevBuf<uint32_t> d_words;
     long long last_nblk = -1;       // blocks the last launched draw left in d_words (-1: none usable)
-    unsigned long long* d_look = nullptr;   // np_write_kernel's look-back words, one per workgroup
-    size_t look_cap = 0;            // workgroups
+    mppi_host::DevBuf<unsigned long long> d_look;   // np_write_kernel's look-back words, one per workgroup
     unsigned long long epoch = 0;   // the last draw's epoch (24 bits; the words are cleared when it wraps)
-    NpResult* d_res = nullptr;
-    NpHostOut* h_out = nullptr;     // coherent host-mapped: the draw's state and status, written by np_state_kernel
-    NpHostOut* d_out = nullptr;     // its device address
-    uint32_t* h_key = nullptr;      // coherent host-mapped: the starting key array, read by the twist kernels
-    uint32_t* d_key = nullptr;      // its device address
-    hipEvent_t done = nullptr;
+    mppi_host::DevBuf<NpResult> d_res;
+    mppi_host::MappedBuf<NpHostOut> h_out;  // coherent host-mapped: the draw's state and status (np_state_kernel)
+    mppi_host::MappedBuf<uint32_t> h_key;   // coherent host-mapped: the starting key array, read by the twist kernels
+    mppi_host::Event done;
     bool pending = false;
 };
 
@@ -571,38 +568,22 @@ int mppi_np_ctx_create(int device, const double* log_params, mppi_np_ctx** out) 
     if (!out || !log_params) return fail(MPPI_E_ARG, "null argument");
     *out = nullptr;
     HIP_TRY(hipSetDevice(device));
-    mppi_np_ctx* c = new mppi_np_ctx();
+    auto c = std::make_unique<mppi_np_ctx>();
     c->device = device;
-    hipError_t e;
-    if ((e = hipMalloc(&c->d_log, NPLOG_NDATA * sizeof(double))) != hipSuccess ||
-        (e = hipMemcpy(c->d_log, log_params, NPLOG_NDATA * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMalloc(&c->d_seq, (size_t)kSeqBlocks * kN * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc(&c->d_res, sizeof(NpResult))) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_out, sizeof(NpHostOut), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void**)&c->d_out, c->h_out, 0)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_key, kN * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void**)&c->d_key, c->h_key, 0)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming)) != hipSuccess) {
-        mppi_np_ctx_destroy(c);
-        return fail(MPPI_E_HIP, std::string("mppi_np_ctx_create: ") + hipGetErrorString(e));
-    }
-    *out = c;
+    if (int rc = c->d_log.alloc(NPLOG_NDATA)) return rc;
+    HIP_TRY(hipMemcpy(c->d_log, log_params, NPLOG_NDATA * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = c->d_seq.alloc((size_t)kSeqBlocks * kN)) return rc;
+    if (int rc = c->d_res.alloc(1)) return rc;
+    if (int rc = c->h_out.alloc(1, mppi_host::kCoherent)) return rc;
+    if (int rc = c->h_key.alloc(kN, mppi_host::kCoherent)) return rc;
+    if (int rc = c->done.create()) return rc;
+    *out = c.release();
     return MPPI_OK;
 }
 
 void mppi_np_ctx_destroy(mppi_np_ctx* c) {
     if (!c) return;
     if (c->pending && c->done) (void)hipEventSynchronize(c->done);
-    (void)hipFree(c->d_log);
-    (void)hipFree(c->d_seq);
-    (void)hipFree(c->d_nibs);
-    (void)hipFree(c->d_jumped);
-    (void)hipFree(c->d_words);
-    (void)hipFree(c->d_look);
-    (void)hipFree(c->d_res);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->h_key) (void)hipHostFree(c->h_key);
-    if (c->done) (void)hipEventDestroy(c->done);
     delete c;
 }
 
@@ -621,10 +602,8 @@ int mppi_np_set_jumps(mppi_np_ctx* c, int block_stride, int streams, const unsig
         return fail(MPPI_E_ARG, "mppi_np_set_jumps: bad stride, stream count or polynomial size");
     HIP_TRY(hipSetDevice(c->device));
     if (c->pending) HIP_TRY(hipEventSynchronize(c->done));   // the buffers may be in use by the last draw
-    (void)hipFree(c->d_nibs);
-    (void)hipFree(c->d_jumped);
-    c->d_nibs = nullptr;
-    c->d_jumped = nullptr;
+    c->d_nibs.reset();
+    c->d_jumped.reset();
     c->poly_P = c->poly_streams = 0;
     if (streams > 1) {
         const int ns = streams - 1;
@@ -646,9 +625,9 @@ int mppi_np_set_jumps(mppi_np_ctx* c, int block_stride, int streams, const unsig
                         nibs[((size_t)ch * G + j / kNibS) * kNibS + j % kNibS] = v;
                 }
             }
-        HIP_TRY(hipMalloc(&c->d_nibs, nibs.size() * sizeof(uint32_t)));
+        if (int rc = c->d_nibs.alloc(nibs.size())) return rc;
         HIP_TRY(hipMemcpy(c->d_nibs, nibs.data(), nibs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&c->d_jumped, (size_t)ns * R * kN * sizeof(uint32_t)));
+        if (int rc = c->d_jumped.alloc((size_t)ns * R * kN)) return rc;
         c->jG = G;
         c->jR = R;
         c->jcpw = cpw;
@@ -685,26 +664,16 @@ int mppi_np_draw(mppi_np_ctx* c, void* stream, const mppi_np_state* st, long lon
         reuse_blk = c->h_out->blk;
     c->last_nblk = -1;   // until this draw's kernels are queued
     const size_t words = (size_t)p.nblk * kN;
-    if (words > c->words_cap) {
-        reuse_blk = -1;
-        (void)hipFree(c->d_words);
-        c->d_words = nullptr;
-        c->words_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_words, words * sizeof(uint32_t)));
-        c->words_cap = words;
-    }
+    bool fresh = false;
+    if (int rc = c->d_words.reserve(words, &fresh)) return rc;
+    if (fresh) reuse_blk = -1;
     const long long nwg = (p.A + kAttPerWG - 1) / kAttPerWG;
-    if ((size_t)nwg > c->look_cap) {
-        (void)hipFree(c->d_look);
-        c->d_look = nullptr;
-        c->look_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_look, nwg * sizeof(unsigned long long)));
-        c->look_cap = (size_t)nwg;
-        c->epoch = 0;   // cleared below
-    }
+    fresh = false;
+    if (int rc = c->d_look.reserve((size_t)nwg, &fresh)) return rc;
+    if (fresh) c->epoch = 0;   // cleared below
     if (++c->epoch >= (1ull << (64 - kLookShift - 2)) || c->epoch == 1) {
         c->epoch = 1;
-        HIP_TRY(hipMemsetAsync(c->d_look, 0, c->look_cap * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(c->d_look, 0, c->d_look.cap * sizeof(unsigned long long), s));
     }
     memcpy(c->h_key, st->key, kN * sizeof(uint32_t));   // read by the kernels over the link (no copy)
     if (p.streams > 1) {
@@ -712,11 +681,11 @@ int mppi_np_draw(mppi_np_ctx* c, void* stream, const mppi_np_state* st, long lon
         if (reuse_blk >= 0)
             seq = c->d_words + (size_t)reuse_blk * kN;   // read before np_gen_kernel rewrites d_words (stream order)
         else
-            hipLaunchKernelGGL(np_seq_kernel, dim3(1), dim3(kTT), 0, s, c->d_key, c->d_seq);
+            hipLaunchKernelGGL(np_seq_kernel, dim3(1), dim3(kTT), 0, s, c->h_key.dev, c->d_seq);
         hipLaunchKernelGGL(np_jumpn_kernel, dim3(c->jR, c->jG), dim3(kJNT), (4 * c->jcpw + kN + 3) * sizeof(uint32_t),
                            s, seq, c->d_nibs, c->jG, c->jcpw, p.streams - 1, c->jR, c->d_jumped);
     }
-    hipLaunchKernelGGL(np_gen_kernel, dim3(p.streams), dim3(kTT), 0, s, c->d_key, c->d_jumped, c->d_words, p.P,
+    hipLaunchKernelGGL(np_gen_kernel, dim3(p.streams), dim3(kTT), 0, s, c->h_key.dev, c->d_jumped, c->d_words, p.P,
                        (int)p.nblk, c->jparts, c->d_res);
     NpShape sh;
     sh.out = (float*)tgt->out_dev;
@@ -738,7 +707,7 @@ int mppi_np_draw(mppi_np_ctx* c, void* stream, const mppi_np_state* st, long lon
                        c->d_look, c->epoch << (kLookShift + 2), c->d_log, sh, p.pairs, n, st->has_gauss ? 1 : 0,
                        st->gauss, c->d_res);
     hipLaunchKernelGGL(np_state_kernel, dim3(1), dim3(kNT), 0, s, c->d_words, (long long)st->pos, c->d_res, p.need,
-                       c->d_out);
+                       c->h_out.dev);
     // the event marks the end of whatever was queued, even after a failed launch: the next draw waits for it
     // before it rewrites the host-mapped key the queued kernels read
     const hipError_t le = hipGetLastError();

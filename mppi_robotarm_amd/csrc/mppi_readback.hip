@@ -73,10 +73,10 @@ struct mppi_readback {
     int slots = 0;
     int nstreams = 0;               // copy streams (0: the copies go on the caller's stream)
     size_t chunk = 0;               // floats per chunk (a multiple of 128)
-    float* ring = nullptr;          // page-locked, slots x chunk floats
-    hipEvent_t ev[kMaxSlots] = {};
-    hipStream_t cs[kMaxStreams] = {};
-    hipEvent_t start = nullptr;     // the caller's stream, before the copies
+    mppi_host::PinnedBuf<float> ring;   // page-locked, slots x chunk floats
+    mppi_host::Event ev[kMaxSlots];
+    mppi_host::Stream cs[kMaxStreams];
+    mppi_host::Event start;         // the caller's stream, before the copies
     bool avx2 = false;
     std::vector<std::thread> pool;
 
@@ -167,30 +167,23 @@ int mppi_readback_create(int device, int workers, int slots, long long chunk_flo
         return fail(MPPI_E_ARG, "mppi_readback_create: workers 1..64, slots 2..16, chunk >= 128 floats, "
                                 "copy streams 0..4");
     *out = nullptr;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(MPPI_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    auto* rb = new mppi_readback();
+    HIP_TRY(hipSetDevice(device));
+    auto rb = std::make_unique<mppi_readback>();
     rb->device = device;
     rb->workers = workers;
     rb->slots = slots;
     rb->chunk = ((size_t)chunk_floats + 127) & ~(size_t)127;   // its eighth stays 16-float aligned
     rb->nstreams = copy_streams;
     rb->avx2 = __builtin_cpu_supports("avx2");
-    e = hipHostMalloc((void**)&rb->ring, rb->chunk * slots * sizeof(float), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        delete rb;
-        return fail(MPPI_E_HIP, std::string("hipHostMalloc (read-back ring): ") + hipGetErrorString(e));
-    }
-    for (int s = 0; s < slots && e == hipSuccess; ++s) e = hipEventCreateWithFlags(&rb->ev[s], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&rb->start, hipEventDisableTiming);
-    for (int s = 0; s < copy_streams && e == hipSuccess; ++s) e = hipStreamCreateWithFlags(&rb->cs[s], hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        mppi_readback_destroy(rb);
-        return fail(MPPI_E_HIP, std::string("mppi_readback_create: ") + hipGetErrorString(e));
-    }
+    if (int rc = rb->ring.alloc(rb->chunk * slots)) return rc;
+    for (int s = 0; s < slots; ++s)
+        if (int rc = rb->ev[s].create()) return rc;
+    if (int rc = rb->start.create()) return rc;
+    for (int s = 0; s < copy_streams; ++s)
+        if (int rc = rb->cs[s].create()) return rc;
     rb->pool.reserve(workers);
-    for (int w = 0; w < workers; ++w) rb->pool.emplace_back([rb, w] { rb->worker(w); });
-    *out = rb;
+    for (int w = 0; w < workers; ++w) rb->pool.emplace_back([p = rb.get(), w] { p->worker(w); });
+    *out = rb.release();
     return MPPI_OK;
 }
 
@@ -202,12 +195,6 @@ void mppi_readback_destroy(mppi_readback* rb) {
     }
     rb->cv.notify_all();
     for (auto& t : rb->pool) t.join();
-    for (int s = 0; s < rb->slots; ++s)
-        if (rb->ev[s]) (void)hipEventDestroy(rb->ev[s]);
-    if (rb->start) (void)hipEventDestroy(rb->start);
-    for (int s = 0; s < rb->nstreams; ++s)
-        if (rb->cs[s]) (void)hipStreamDestroy(rb->cs[s]);
-    if (rb->ring) (void)hipHostFree(rb->ring);
     delete rb;
 }
 

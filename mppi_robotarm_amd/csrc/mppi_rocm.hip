@@ -746,27 +746,27 @@ struct mppi_ctx {
     KConst kc;
     ClampK ck{};                // torque limits (mode 0: none)
     StepStatic stat{};          // x0 + window of the next launch (a kernel argument)
-    DevStep* d_step = nullptr;  // [2] ping-pong nominal
+    mppi_host::DevBuf<DevStep> d_step;      // [2] ping-pong nominal
     int cur = 0;
-    DevStep* h_step = nullptr;  // pinned staging of an uploaded nominal
-    hipEvent_t staged = nullptr;
+    mppi_host::PinnedBuf<DevStep> h_step;   // pinned staging of an uploaded nominal
+    mppi_host::Event staged;
     bool stage_pending = false;     // a staging copy may still be reading h_step
     // the current device nominal is the one the last MPPI_FLAG_HOST_OUT launch
     // published (h_dout): a drop-in step whose u equals it uploads nothing
     bool nominal_published = false;
     bool x_flipped = false;          // the last launch flipped the ping-pong and exchanged (undone on MPPI_E_EXCHANGE)
-    double* h_dout = nullptr;       // coherent host-mapped drop-in outputs (HostOut layout)
-    double* d_dout = nullptr;       // its device view
+    mppi_host::MappedBuf<double> h_dout;   // coherent host-mapped drop-in outputs (HostOut layout)
     unsigned dseq = 0;
     double dropin_us[6] = {};       // phase ends of the last mppi_step_dropin (mppi_debug_dropin_times)
     mppi_host::Handoff hand;        // hand-off form, its buffers and the time-out words
-    double* d_weps = nullptr;
-    double* h_buf = nullptr;    // pinned D2H staging, 2 * kMaxT doubles
-    float2* d_base = nullptr;   // traj base controls
-    float2* h_base = nullptr;   // pinned
-    float2* d_upd = nullptr;    // updated, unshifted controls of the last fused update (optimal trajectory)
+    mppi_host::DevBuf<double> d_weps;
+    mppi_host::PinnedBuf<double> h_buf;     // pinned D2H staging, 2 * kMaxT doubles
+    mppi_host::DevBuf<float2> d_base;       // traj base controls
+    mppi_host::PinnedBuf<float2> h_base;
+    mppi_host::DevBuf<float2> d_upd;        // updated, unshifted controls of the last fused update (optimal trajectory)
     bool upd_valid = false;
-    double* h_out = nullptr;    // pinned: nominal (2T fp64) + optimal trajectory (4T fp32) of mppi_get_step_outputs
+    // pinned: nominal (2T fp64) + optimal trajectory (4T fp32) of mppi_get_step_outputs
+    mppi_host::PinnedBuf<double> h_out;
     mppi_dropin_binding bind{};  // mppi_dropin_bind
     bool bound = false;
     std::chrono::steady_clock::time_point tick_t0{};   // start of the current mppi_dropin_tick (phase times)
@@ -840,7 +840,7 @@ int auto_lps(int K_local) {
 }
 
 // The device side of mppi_ctx_create: the hand-off form from the rollout kernel's occupancy, then every
-// buffer (on an error the caller destroys the half-built context).
+// buffer (on an error the caller deletes the half-built context, whose members free what they hold).
 int alloc(mppi_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     int ncu = 0, per_cu = 0;
@@ -852,19 +852,16 @@ int alloc(mppi_ctx* c) {
     });
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + 2 * c->cfg.T, 0)) return rc;
     c->kc.acquire = c->hand.acquire;
-    HIP_TRY(hipMalloc(&c->d_step, 2 * sizeof(DevStep)));
-    HIP_TRY(hipMalloc(&c->d_weps, 2 * kMaxT * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->d_base, kMaxT * sizeof(float2)));
-    HIP_TRY(hipMalloc(&c->d_upd, kMaxT * sizeof(float2)));
-    HIP_TRY(hipHostMalloc(&c->h_out, 2 * kMaxT * sizeof(double) + 4 * kMaxT * sizeof(float), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&c->h_step, sizeof(DevStep), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&c->h_buf, 2 * kMaxT * sizeof(double), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&c->h_base, kMaxT * sizeof(float2), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&c->h_dout, (4 + 2 * kMaxT) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void**)&c->d_dout, c->h_dout, 0));
-    HIP_TRY(hipEventCreateWithFlags(&c->staged, hipEventDisableTiming));
-    HIP_TRY(hipMemset(c->d_step, 0, 2 * sizeof(DevStep)));
-    HIP_TRY(hipMemset(c->d_weps, 0, 2 * kMaxT * sizeof(double)));
+    if (int rc = c->d_step.alloc_zeroed(2)) return rc;
+    if (int rc = c->d_weps.alloc_zeroed(2 * kMaxT)) return rc;
+    if (int rc = c->d_base.alloc(kMaxT)) return rc;
+    if (int rc = c->d_upd.alloc(kMaxT)) return rc;
+    if (int rc = c->h_out.alloc(4 * kMaxT)) return rc;   // 2 kMaxT fp64, then 4 kMaxT fp32
+    if (int rc = c->h_step.alloc(1)) return rc;
+    if (int rc = c->h_buf.alloc(2 * kMaxT)) return rc;
+    if (int rc = c->h_base.alloc(kMaxT)) return rc;
+    if (int rc = c->h_dout.alloc(4 + 2 * kMaxT, mppi_host::kCoherent)) return rc;
+    if (int rc = c->staged.create()) return rc;
     HIP_TRY(hipDeviceSynchronize());
     memset(c->h_step, 0, sizeof(DevStep));
     memset(c->h_dout, 0, (4 + 2 * kMaxT) * sizeof(double));
@@ -898,7 +895,7 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
     const double* S = cfg->sigma;
     const double det = S[0] * S[3] - S[1] * S[2];
     if (det == 0.0 || !isfinite(det)) return fail(MPPI_E_SINGULAR, "Singular matrix");
-    mppi_ctx* c = new mppi_ctx();
+    auto c = std::make_unique<mppi_ctx>();
     c->cfg = *cfg;
     c->device = device;
     c->stream = (hipStream_t)stream;
@@ -907,10 +904,8 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
     c->sig_inv[2] = -S[2] / det;
     c->sig_inv[3] = S[0] / det;
     int lps = cfg->lanes_per_sample > 0 ? cfg->lanes_per_sample : auto_lps(cfg->K_local);
-    if (lps != 1 && lps != 2 && lps != 4 && lps != 8 && lps != 16) {
-        delete c;
+    if (lps != 1 && lps != 2 && lps != 4 && lps != 8 && lps != 16)
         return fail(MPPI_E_ARG, "lanes_per_sample must be 0, 1, 2, 4, 8 or 16");
-    }
     c->lps = lps;
     // 512-thread workgroups when the grid fills every CU with one of them (8 waves:
     // two per SIMD); 256 otherwise.  MPPI_BLOCK=256|512 overrides (diagnostics).
@@ -920,10 +915,7 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
     // a workgroup's merge thread owns one column of the 2T + 1 merged columns
     if (2 * cfg->T + 1 > c->nt) c->nt = 512;
     c->nblocks = (int)((lanes + c->nt - 1) / c->nt);
-    if (c->nblocks > 1024 * 1024) {
-        delete c;
-        return fail(MPPI_E_ARG, "too many samples");
-    }
+    if (c->nblocks > 1024 * 1024) return fail(MPPI_E_ARG, "too many samples");
     const mppi_arm_params& a = cfg->arm;
     KConst& k = c->kc;
     memset(&k, 0, sizeof(k));
@@ -953,11 +945,8 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
         ck.v_hi[d] = (float)ck.u_hi[d];
     }
 
-    if (int rc = alloc(c)) {
-        mppi_ctx_destroy(c);
-        return rc;
-    }
-    *out = c;
+    if (int rc = alloc(c.get())) return rc;
+    *out = c.release();
     return MPPI_OK;
 }
 
@@ -965,18 +954,6 @@ void mppi_ctx_destroy(mppi_ctx* c) {
     if (!c) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipDeviceSynchronize();
-    (void)hipFree(c->d_step);
-    c->hand.release();
-    (void)hipFree(c->d_weps);
-    (void)hipFree(c->d_base);
-    (void)hipFree(c->d_upd);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    c->ex.release();
-    if (c->h_step) (void)hipHostFree(c->h_step);
-    if (c->h_buf) (void)hipHostFree(c->h_buf);
-    if (c->h_base) (void)hipHostFree(c->h_base);
-    if (c->h_dout) (void)hipHostFree(c->h_dout);
-    if (c->staged) (void)hipEventDestroy(c->staged);
     delete c;
 }
 
@@ -1042,7 +1019,7 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
 HostOut next_host_out(mppi_ctx* c, unsigned flags) {
     if (!(flags & MPPI_FLAG_HOST_OUT)) return HostOut{nullptr, 0u};
     if (++c->dseq == 0) ++c->dseq;
-    return HostOut{c->d_dout, c->dseq};
+    return HostOut{c->h_dout.dev, c->dseq};
 }
 
 // Wait until the last MPPI_FLAG_HOST_OUT launch has published its outputs: a spin
@@ -1051,7 +1028,7 @@ HostOut next_host_out(mppi_ctx* c, unsigned flags) {
 int wait_host_out(mppi_ctx* c) {
     if (c->dseq == 0) return fail(MPPI_E_ARG, "no MPPI_FLAG_HOST_OUT launch to wait for");
     const unsigned seq = c->dseq;
-    volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(c->h_dout);
+    volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(c->h_dout.h);
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned long long n = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq; ++n) {
         if ((n & 1023) == 1023) {
@@ -1140,8 +1117,8 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
     with_rollout(c, c->hand.poll, [&](auto lps, auto nt, auto p, auto cl) {
         hipLaunchKernelGGL((rollout_kernel<lps, nt, p, cl>), dim3(c->nblocks), dim3(nt), 0, c->stream, c->kc, c->stat, cur,
                            nz, S_dev, c->hand.d_slab, c->hand.d_gslab, c->hand.d_counter, partial_dev, c->d_weps, nxt,
-                           flags, c->ex.xd, c->hand.d_epoch, c->hand.d_tmo, reinterpret_cast<float*>(c->d_upd), ho,
-                           c->d_dbg, c->ck);
+                           flags, c->ex.xd, c->hand.d_epoch, c->hand.h_tmo.dev, reinterpret_cast<float*>(c->d_upd.h),
+                           ho, c->d_dbg, c->ck);
     });
     const int rc = launch_check("rollout_kernel");
     if (took_update(c, rc, flags)) c->x_flipped = (flags & MPPI_FLAG_EXCHANGE) != 0;   // undone if the exchange fails
@@ -1176,7 +1153,7 @@ int mppi_merge_partials(mppi_ctx* c, const double* partials_dev, int n, unsigned
     auto* f = big ? (cl ? merge_kernel<512, true> : merge_kernel<512, false>)
                   : (cl ? merge_kernel<256, true> : merge_kernel<256, false>);
     hipLaunchKernelGGL(f, dim3(1), dim3(big ? 512 : 256), 0, c->stream, c->kc, partials_dev, n, c->d_weps, cur, nxt,
-                       flags, reinterpret_cast<float*>(c->d_upd), ho, c->ck);
+                       flags, reinterpret_cast<float*>(c->d_upd.h), ho, c->ck);
     const int rc = launch_check("merge_kernel");
     took_update(c, rc, flags);
     return rc;

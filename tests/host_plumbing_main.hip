@@ -1,13 +1,14 @@
 // Stand-alone host program over csrc/mppi_host.h (tests/test_host_plumbing.py builds it host-only under
-// AddressSanitizer and UBSan and compares its output with NumPy).  No device is touched: only the helpers
-// that make no HIP call.  One command per line on stdin, doubles as C hex floats; one result line each
-// (a window: one line per slot array).
+// AddressSanitizer and UBSan and compares its output with NumPy).  No device is touched: the helpers make no
+// HIP call, and `owners` runs where none is visible, so its HIP calls fail.  One command per line on stdin,
+// doubles as C hex floats; one result line each (a window: one line per slot array; owners: one per member).
 //   window W <4 W doubles>               -> win / key / ctr as fp32 bit patterns
 //   exploit <param_exploration> K_total  -> k_exploit
 //   gamma <gamma> <lambda> <alpha>       -> the resolved gamma
 //   geometry K_local K_total k_offset    -> return code
 //   timeout w0 w1                        -> return code, verdict bits, the two words afterwards, the message
 //   handoff nblocks ncu per_cu stride extra_words -> form and sizes
+//   owners                               -> per failing member: return code, 1 if the owner stayed empty, the message
 #include <stdio.h>
 #include <string.h>
 
@@ -25,6 +26,37 @@ void print_slots(const char* name, const float4* v, int n) {
     printf("%s", name);
     for (int j = 0; j < n; ++j) printf(" %08x %08x %08x %08x", bits(v[j].x), bits(v[j].y), bits(v[j].z), bits(v[j].w));
     printf("\n");
+}
+
+void owner_line(const char* name, int rc, bool empty) {
+    printf("owners %s %d %d %s\n", name, rc, (int)empty, rc ? mppi_host::last_error() : "");
+}
+
+// Every member of the owners that can fail, where no device is visible: the return code, whether the owner is
+// still empty, the message.  Each is reset twice afterwards and destructed at the end of the function.
+void owners() {
+    using namespace mppi_host;
+    DevBuf<double> dev;
+    owner_line("DevBuf.alloc", dev.alloc(16), !dev && dev.cap == 0);
+    owner_line("DevBuf.alloc_zeroed", dev.alloc_zeroed(16), !dev && dev.cap == 0);
+    bool fresh = false;
+    owner_line("DevBuf.reserve", dev.reserve(16, &fresh), !dev && dev.cap == 0 && fresh);
+    fresh = false;
+    owner_line("DevBuf.reserve0", dev.reserve(0, &fresh), !dev && dev.cap == 0 && !fresh);   // nothing to do: MPPI_OK
+    PinnedBuf<float> pinned;
+    owner_line("PinnedBuf.alloc", pinned.alloc(16), !pinned);
+    MappedBuf<unsigned> mapped;
+    owner_line("MappedBuf.alloc", mapped.alloc(64, kCoherent), !mapped && !mapped.dev);
+    Event ev;
+    owner_line("Event.create", ev.create(), !ev);
+    Stream st;
+    owner_line("Stream.create", st.create(), !st);
+    for (int i = 0; i < 2; ++i) dev.reset(), pinned.reset(), mapped.reset(), ev.reset(), st.reset();
+    Handoff hand;
+    owner_line("Handoff.setup", hand.setup(256, 256, 1, 130, 0), !hand.d_slab && !hand.d_counter && !hand.h_tmo);
+    Exchange ex;
+    hipIpcMemHandle_t handle;
+    owner_line("Exchange.handle", ex.handle(0, 130, 2, &handle), !ex.d_inbox && ex.world_alloc == 0);
 }
 }  // namespace
 
@@ -69,6 +101,8 @@ int main() {
             h.plan(nblocks, ncu, per_cu, stride, extra);
             printf("handoff %d %d %d %zu %zu %zu %zu\n", (int)h.poll, h.acquire, h.ngroups, h.slab, h.gslab, h.extra_off,
                    h.ctr_bytes);
+        } else if (!strcmp(cmd, "owners")) {
+            owners();
         } else {
             return 2;
         }

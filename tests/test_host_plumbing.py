@@ -66,7 +66,9 @@ def results(tmp_path_factory):
     lines += [f"geometry {kl} {kt} {ko}" for kl, kt, ko, _ in GEOMETRY]
     lines += [f"timeout {a} {b}" for a, b in TIMEOUT]
     lines += ["handoff " + " ".join(str(v) for v in h) for h in HANDOFF]
+    lines += ["owners"]
     env = {k: v for k, v in os.environ.items() if k != "MPPI_HANDOFF"}
+    env.update(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")   # owners: no device, wherever this runs
     r = subprocess.run([str(exe)], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=60)
     assert r.returncode == 0, r.stderr[-2000:]
     out = {}
@@ -164,3 +166,26 @@ def test_handoff_sizes(results):
         # the arrival counters and the epoch word fit below the extra words, which start 256-B aligned
         assert extra_off * 4 % 256 == 0 and 0 <= extra_off * 4 - (ngroups + 2) * 4 < 256
         assert ctr_bytes == (extra_off + extra) * 4
+
+
+OWNERS = {"DevBuf.alloc": "hipMalloc", "DevBuf.alloc_zeroed": "hipMalloc", "DevBuf.reserve": "hipMalloc",
+          "PinnedBuf.alloc": "hipHostMalloc", "MappedBuf.alloc": "hipHostMalloc",
+          "Event.create": "hipEventCreateWithFlags", "Stream.create": "hipStreamCreateWithFlags",
+          "Handoff.setup": "hipMalloc", "Exchange.handle": "hipSetDevice"}
+
+
+def test_owners_without_device(results):
+    """No device is visible: every member that allocates or creates fails with MPPI_E_HIP, its message names the
+    HIP call (<failing HIP call>: <hipGetErrorString>), and the owner stays empty; reserve(0) has nothing to do.
+    The double reset() and the destructors are the sanitizers' to judge (the fixture's exit status)."""
+    got = {}
+    for text in results["owners"]:
+        name, rc, empty, *msg = text.split(" ", 3)
+        got[name] = (int(rc), int(empty), msg[0] if msg else "")
+    assert got.pop("DevBuf.reserve0") == (N.MPPI_OK, 1, "")
+    assert set(got) == set(OWNERS)
+    for name, call in OWNERS.items():
+        rc, empty, msg = got[name]
+        assert rc == N.MPPI_E_HIP and empty == 1, name
+        expr, _, err = msg.rpartition(": ")
+        assert expr.startswith(call + "(") and err, (name, msg)
