@@ -369,16 +369,36 @@ typedef struct {
                                                lane p the link pair (2p, 2p+1))           */
     double param_gamma;                     /* as mppi_config.param_gamma: control.py:45's
                                                gamma as given; NaN = lambda (1 - alpha)  */
+    /* Torque limits per joint d < n, with mppi_config.clamp_mode's semantics (_g,
+     * control.py:166-172, switched on):
+     *   0  off (a zeroed config, mppi_chain_config_init);
+     *   1  every sampled control v = u_t + eps (eps alone for an exploration sample) is
+     *      clipped to [u_min, u_max] before the dynamics and before the control-cost term
+     *      a_t . v — in fp32 against the limits rounded to nearest (fp32 rollout), in
+     *      fp64 against the limits themselves (precision 1); the weights and the weighted
+     *      sums still take the unclamped eps; the trajectory re-rolls clip the control
+     *      they feed to the dynamics (the host trajectories in fp64);
+     *   2  also the updated nominal u += w_eps is clipped, in fp64, wherever the update
+     *      runs on the device (MPPI_FLAG_FUSED_UPDATE, in the rollout or the merge
+     *      launch), before the next launch's a_t and fp32 rows are built from it and
+     *      before the shift: the reference with visualize_optimal_traj (mode 1: without).
+     * u_min[d] <= u_max[d]; +-inf stands for an absent limit; entries d >= n are ignored. */
+    int clamp_mode;
+    double u_min[MPPI_CHAIN_MAX_DOF];
+    double u_max[MPPI_CHAIN_MAX_DOF];
 } mppi_chain_config;
 
 typedef struct mppi_chain_ctx mppi_chain_ctx;
 
 /* As mppi_config_init for the chain: every field zero except param_gamma = NaN
  * (lambda (1 - alpha)) and chain.g = 9.81 (sys_params.py:13); the caller sets n,
- * the link parameters, Sigma and the rest.  No device call. */
+ * the link parameters, Sigma and the rest.  clamp_mode stays 0: no torque limits.
+ * No device call. */
 void mppi_chain_config_init(mppi_chain_config *cfg);
 
-/* control.py:21-65 with the chain model; MPPI_E_SINGULAR if Sigma is not SPD. */
+/* control.py:21-65 with the chain model; MPPI_E_SINGULAR if Sigma is not SPD;
+ * MPPI_E_ARG for a clamp_mode outside 0..2 or, with clamp_mode > 0, a NaN limit or
+ * u_min[d] > u_max[d] for some d < n (checked before any device call). */
 int mppi_chain_ctx_create(const mppi_chain_config *cfg, int device, void *stream, mppi_chain_ctx **out);
 void mppi_chain_ctx_destroy(mppi_chain_ctx *ctx);
 int mppi_chain_set_stream(mppi_chain_ctx *ctx, void *stream);
@@ -426,8 +446,10 @@ int mppi_chain_debug_set_buffer(mppi_chain_ctx *ctx, void *dbg_dev);
 /* Tests only: one rollout (as mppi_chain_rollout with no flags; S_dev nullable)
  * through a build of the same kernel that also records the window slot every
  * sample picked at every step (the argmin of control.py:205-215 inside _c),
- * slots_dev int32 [K_local][T].  7-link contexts only.  The parity tests use it
- * to recompute a sample's fp64 cost with the device's own picks. */
+ * slots_dev int32 [K_local][T].  7-link contexts only, and only without torque
+ * limits (the recording instances are unclamped: MPPI_E_ARG with clamp_mode > 0).
+ * The parity tests use it to recompute a sample's fp64 cost with the device's own
+ * picks. */
 int mppi_chain_debug_slots(mppi_chain_ctx *ctx, const float *noise_dev, double *S_dev, int *slots_dev);
 
 /* ------------------------------------------------------------------------

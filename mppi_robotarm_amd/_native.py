@@ -113,11 +113,13 @@ class ChainConfigC(C.Structure):
         ("stage_cost_weight", C.c_double * 4), ("terminal_cost_weight", C.c_double * 4),
         ("chain", ChainParamsC), ("precision", C.c_int), ("lanes_per_sample", C.c_int),
         ("param_gamma", C.c_double),
+        # torque limits per joint (_g, control.py:166-172): 0 off, 1 sampled controls, 2 also the updated nominal
+        ("clamp_mode", C.c_int), ("u_min", C.c_double * CHAIN_MAX_DOF), ("u_max", C.c_double * CHAIN_MAX_DOF),
     ]
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
-        if "param_gamma" not in kw and len(args) < len(self._fields_):
+        if "param_gamma" not in kw and len(args) <= [f for f, _ in self._fields_].index("param_gamma"):
             self.param_gamma = float("nan")   # gamma = lambda (1 - alpha), control.py:45
 
 

@@ -99,12 +99,18 @@ class ChainEngine(_Engine):
                  stage_cost_weight, terminal_cost_weight, param_exploration: float = 0.0,
                  chain: ChainParams = ChainParams(), K_total: int | None = None, k_offset: int = 0,
                  device: int | torch.device | None = None, precision: str = "f32", lanes_per_sample: int = 0,
-                 param_gamma: float | None = None):
+                 param_gamma: float | None = None, u_min=None, u_max=None, clamp_nominal: bool = True):
+        """u_min / u_max: torque limits per joint (a scalar or n values; None or +-inf: no limit on that side),
+        as RolloutEngine's: every sampled control is clipped before the dynamics and the control cost (in the
+        rollout's own precision), the re-rolled trajectories clip theirs, and with clamp_nominal (the reference
+        with visualize_optimal_traj) the fused update clips the nominal too.  The context rejects NaN limits
+        and u_min > u_max (ValueError)."""
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
         self.precision = precision
         self.n = chain.n
         cfg = N.ChainConfigC()
+        self._set_limits(cfg, self.n, u_min, u_max, clamp_nominal)
         cfg.delta_t, cfg.param_lambda = float(delta_t), float(param_lambda)
         cfg.param_alpha, cfg.param_exploration = float(param_alpha), float(param_exploration)
         sig = np.asarray(sigma, dtype=np.float64)
@@ -163,7 +169,14 @@ class ChainMPPIController(MPPIControllerBase):
     more than one sample carries weight; so after each fp32 step the spread of its weights, eta - 1 =
     sum_k exp(-(S_k - min S) / lambda) - 1 (mppi_chain_last_eta), is checked, and a step whose weights spread
     (eta - 1 > ETA_TOL) is run again in fp64 from the same inputs, as are the steps after it until the weights
-    are one-hot again.  run.py's lambda = 100 keeps them one-hot (eta - 1 ~ 0): the fp32 step alone."""
+    are one-hot again.  run.py's lambda = 100 keeps them one-hot (eta - 1 ~ 0): the fp32 step alone.
+
+    ``u_min`` / ``u_max``: torque limits, a scalar or one value per joint (properties, re-read on every call:
+    rebinding either rebuilds the engines before the next step), with the arm controller's meaning — the
+    reference's clamp hook ``_g`` (control.py:166-172) switched on: the sampled controls are clipped before the
+    dynamics and the control cost, the weights still multiply the unclamped noise, and with
+    ``visualize_optimal_traj`` the updated nominal is clipped too.  Both engines of ``precision="auto"`` carry
+    them."""
 
     ETA_TOL = 1e-6   # weight outside the best sample above which precision="auto" takes the fp64 rollout
 
@@ -175,7 +188,7 @@ class ChainMPPIController(MPPIControllerBase):
                  visualize_optimal_traj=True, visualze_sampled_trajs=False, *, chain: ChainParams = ChainParams(),
                  u_init=None, device: int | None = None, verbose: bool = False, noise: str = "numpy", seed: int = 0,
                  process_group=None, exchange: str = "auto", precision: str = "auto",
-                 numpy_noise_on_device: bool = True) -> None:
+                 numpy_noise_on_device: bool = True, u_min=None, u_max=None) -> None:
         self.chain = chain
         if precision not in ("auto", "f32", "f64"):
             raise ValueError("precision must be 'auto', 'f32' or 'f64'")
@@ -193,6 +206,8 @@ class ChainMPPIController(MPPIControllerBase):
         self.prev_waypoints_idx = 0
         super().__init__(device=device, verbose=verbose, noise=noise, seed=seed, process_group=process_group,
                          exchange=exchange, numpy_noise_on_device=numpy_noise_on_device)
+        self.u_min, self.u_max = u_min, u_max   # properties (MPPIControllerBase): torque limits of _g, validated
+        self._limits()                          # u_min <= u_max
         self._slots = {}               # rollout precision -> the parked state of its engine (_SLOT fields)
         self._active = None            # the precision whose engine the per-engine fields hold
         self._spread = False           # precision="auto": the last step's weights were spread (next step fp64)
@@ -220,8 +235,8 @@ class ChainMPPIController(MPPIControllerBase):
         self._active = precision
 
     def _engine_key(self):
-        """The shared key plus the chain and the rollout precision."""
-        return super()._engine_key() + (self.chain, self._active)
+        """The shared key plus the chain, the rollout precision and the torque limits with their mode."""
+        return super()._engine_key() + (self.chain, self._active, self._clamp_key())
 
     def _get_engine(self, key=None) -> ChainEngine:
         key = self._engine_key() if key is None else key
@@ -233,10 +248,12 @@ class ChainMPPIController(MPPIControllerBase):
             device = self._device if self._device is not None else torch.cuda.current_device()
             # gamma is fixed at construction in the reference (control.py:45) while lambda is
             # re-read per call: the engine takes gamma as given, as the 2-link engine does
+            lo, hi = self._limits() or (None, None)
             self._engine = ChainEngine(K_local, self.T, self.delta_t, self.param_lambda, self.param_alpha, self.Sigma,
                                        self.stage_cost_weight, self.terminal_cost_weight, self.param_exploration,
                                        self.chain, K_total=self.K, k_offset=k_offset, device=device,
-                                       precision=self._active, param_gamma=self.param_gamma)
+                                       precision=self._active, param_gamma=self.param_gamma, u_min=lo, u_max=hi,
+                                       clamp_nominal=bool(self.visualize_optimal_traj))
             self._noise_dev = self._engine.new_noise()
             self._noise_alt = None                         # the queued draw's buffer, made on first use
             self._partial = self._engine.new_partial()
@@ -373,6 +390,7 @@ class ChainMPPIController(MPPIControllerBase):
         un = u + w_epsilon                                            # control.py:126 (u itself untouched here)
         optimal_traj = np.zeros((self.T, self.dim_x))
         if self.visualize_optimal_traj:
+            self._g(un)                                    # _g(u[t-1]) for every row, in place (control.py:133)
             optimal_traj = eng.optimal_traj_host(x0, un)
         if self.visualze_sampled_trajs:
             tr = eng.trajectories(base_u=None, noise=self._noise_dev)

@@ -143,64 +143,6 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
     def host_update(self, value) -> None:
         self._host_update = bool(value)
 
-    # ------------------------------------------------------------ torque limits (_g, control.py:166-172)
-    @staticmethod
-    def _limit(name: str, value):
-        """A limit as the controller stores it: None, or a read-only fp64 (2,) array (a scalar is broadcast)."""
-        if value is None:
-            return None
-        a = np.asarray(value, dtype=np.float64)
-        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != 2):
-            raise ValueError(f"{name} must be a scalar or have one value per control component (2)")
-        a = np.array(np.broadcast_to(a, (2,)))
-        if np.isnan(a).any():
-            raise ValueError(f"{name} must not be NaN (use +-inf or None for no limit)")
-        a.setflags(write=False)     # rebind to change: the engine key reads the bytes cached at the assignment
-        return a
-
-    @property
-    def u_min(self):
-        """Lower torque limits, fp64 (2,), or None; with u_max the np.clip bounds of _g.  Read on every call like
-        the reference's other attributes: rebinding either rebuilds the engine before the next step."""
-        return self._u_min
-
-    @u_min.setter
-    def u_min(self, value) -> None:
-        self._u_min = self._limit("u_min", value)
-        self._limits_key = None
-
-    @property
-    def u_max(self):
-        """Upper torque limits, fp64 (2,), or None."""
-        return self._u_max
-
-    @u_max.setter
-    def u_max(self, value) -> None:
-        self._u_max = self._limit("u_max", value)
-        self._limits_key = None
-
-    def _limits(self):
-        """(lo, hi) fp64 (2,) with +-inf for an absent side, or None without limits; ValueError if lo > hi."""
-        lo, hi = self._u_min, self._u_max
-        if lo is None and hi is None:
-            return None
-        lo = np.full(2, -np.inf) if lo is None else lo
-        hi = np.full(2, np.inf) if hi is None else hi
-        if (lo > hi).any():
-            raise ValueError(f"u_min {lo.tolist()} exceeds u_max {hi.tolist()}")
-        return lo, hi
-
-    def _clamp_key(self):
-        """What the engine bakes in of the limits: its clamp mode (2: _g also clips the updated nominal, which
-        the reference does in its optimal-trajectory loop, so with visualize_optimal_traj only; control.py:130-133)
-        and the limits' bytes; (0,) without limits."""
-        if self._limits_key is None:
-            lim = self._limits()
-            self._limits_key = () if lim is None else (lim[0].tobytes(), lim[1].tobytes())
-        if not self._limits_key:
-            return (0,)
-        return (2 if self.visualize_optimal_traj else 1,) + self._limits_key
-
     # ------------------------------------------------------------ engine
     def _engine_key(self):
         """The shared key plus the kinematics lengths self.l1/l2 (control.py:178-179,205-206), the arm
@@ -513,14 +455,6 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
         return u[0], u, optimal_traj, sampled_traj_list
 
     # ------------------------------------------------------------ host helpers (reference semantics)
-    def _g(self, v: np.ndarray) -> float:
-        """clamp input (control.py:166-172, whose two np.clip lines are commented out): with u_min / u_max
-        set, v (one control, or rows of them) is clipped in place, as those lines would; else the identity"""
-        lim = self._limits()
-        if lim is not None:
-            np.clip(v, lim[0], lim[1], out=v)
-        return v
-
     def _get_nearest_waypoint(self, q1: float, q2: float, update_prev_idx: bool = False):
         """search the closest waypoint (control.py:200-232), host fp64"""
         prev_idx = self.prev_waypoints_idx

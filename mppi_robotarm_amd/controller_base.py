@@ -126,7 +126,9 @@ class MPPIControllerBase:
     """What MPPIControllerForPathTracking and ChainMPPIController share.  A subclass sets the reference's
     attributes (K, T, dim_u, dim_x, Sigma, the cost weights, visualze_sampled_trajs, ...), has a ``host_update``
     attribute or property (the update of control.py:120-149 runs on the host) and a ``_get_engine(key)`` that
-    builds its engine and that engine's buffers."""
+    builds its engine and that engine's buffers.  The torque limits (``u_min`` / ``u_max``, the clamp hook _g)
+    are kept here, sized by ``dim_u``: a subclass assigns them after ``dim_u`` and appends ``_clamp_key()`` to
+    its engine key."""
 
     def __init__(self, *, device, verbose: bool, noise: str, seed: int, process_group, exchange: str,
                  numpy_noise_on_device: bool) -> None:
@@ -159,6 +161,72 @@ class MPPIControllerBase:
         self._noise_alt = None         # the second noise buffer: the queued draw writes it while a step reads the other
         self._np_stream = None         # the stream of the queued draws (concurrent with the step)
         self._np_ev = None
+
+    # ------------------------------------------------------------ torque limits (_g, control.py:166-172)
+    def _limit(self, name: str, value):
+        """A limit as the controller stores it: None, or a read-only fp64 (dim_u,) array (a scalar is broadcast)."""
+        if value is None:
+            return None
+        n = self.dim_u
+        a = np.asarray(value, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+            raise ValueError(f"{name} must be a scalar or have one value per control component ({n})")
+        a = np.array(np.broadcast_to(a, (n,)))
+        if np.isnan(a).any():
+            raise ValueError(f"{name} must not be NaN (use +-inf or None for no limit)")
+        a.setflags(write=False)     # rebind to change: the engine key reads the bytes cached at the assignment
+        return a
+
+    @property
+    def u_min(self):
+        """Lower torque limits, fp64 (dim_u,), or None; with u_max the np.clip bounds of _g.  Read on every call like
+        the reference's other attributes: rebinding either rebuilds the engine before the next step."""
+        return self._u_min
+
+    @u_min.setter
+    def u_min(self, value) -> None:
+        self._u_min = self._limit("u_min", value)
+        self._limits_key = None
+
+    @property
+    def u_max(self):
+        """Upper torque limits, fp64 (dim_u,), or None."""
+        return self._u_max
+
+    @u_max.setter
+    def u_max(self, value) -> None:
+        self._u_max = self._limit("u_max", value)
+        self._limits_key = None
+
+    def _limits(self):
+        """(lo, hi) fp64 (dim_u,) with +-inf for an absent side, or None without limits; ValueError if lo > hi."""
+        lo, hi = self._u_min, self._u_max
+        if lo is None and hi is None:
+            return None
+        lo = np.full(self.dim_u, -np.inf) if lo is None else lo
+        hi = np.full(self.dim_u, np.inf) if hi is None else hi
+        if (lo > hi).any():
+            raise ValueError(f"u_min {lo.tolist()} exceeds u_max {hi.tolist()}")
+        return lo, hi
+
+    def _clamp_key(self):
+        """What the engine bakes in of the limits: its clamp mode (2: _g also clips the updated nominal, which
+        the reference does in its optimal-trajectory loop, so with visualize_optimal_traj only; control.py:130-133)
+        and the limits' bytes; (0,) without limits."""
+        if self._limits_key is None:
+            lim = self._limits()
+            self._limits_key = () if lim is None else (lim[0].tobytes(), lim[1].tobytes())
+        if not self._limits_key:
+            return (0,)
+        return (2 if self.visualize_optimal_traj else 1,) + self._limits_key
+
+    def _g(self, v: np.ndarray) -> float:
+        """clamp input (control.py:166-172, whose two np.clip lines are commented out): with u_min / u_max
+        set, v (one control, or rows of them) is clipped in place, as those lines would; else the identity"""
+        lim = self._limits()
+        if lim is not None:
+            np.clip(v, lim[0], lim[1], out=v)
+        return v
 
     # ------------------------------------------------------------ engine
     def _shard(self):

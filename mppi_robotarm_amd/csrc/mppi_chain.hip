@@ -17,6 +17,11 @@
 //    with T*N columns per partial row (MAXCH = 4 column chunks).
 //  * chain_traj_kernel<N, NOISE>, chain_philox_kernel: trajectory re-roll and
 //    counter-based Gaussian noise with an n x n Cholesky factor.
+//  * torque limits (mppi_chain_config.clamp_mode; the reference's clamp hook _g, control.py:166-172, switched
+//    on, per joint): the CLAMP instantiations of the rollout, merge and trajectory kernels clip every sampled
+//    control (v_med3_f32 in the fp32 forms, fp64 compares in the fp64 one) and, in mode 2, the updated nominal
+//    in fp64.  The limits travel in ChainClampK, the kernels' last argument, which the other instantiations
+//    never read.
 //
 // C ABI: include/mppi_rocm.h (mppi_chain_*).
 #include <hip/hip_runtime.h>
@@ -71,6 +76,30 @@ struct ChainConst {
     double sig_inv[kCMax * kCMax];
 };
 
+// Torque limits (mppi_chain_config.clamp_mode, u_min, u_max: _g of control.py:166-172 switched on, per joint):
+// the fp64 limits (the fp64 rollout, the nominal's clamp) and their nearest fp32 values (the fp32 rollouts and
+// re-rolls); entries d >= n are -inf / +inf.  The last argument of every kernel that takes it, read by the
+// CLAMP instantiations only: the others keep the instructions they had without it (it is not part of
+// ChainConst, whose growth would move the SGPR allocation of kernels that never read the limits).
+struct ChainClampK {
+    double u_lo[kCMax], u_hi[kCMax];
+    float v_lo[kCMax], v_hi[kCMax];
+    int mode;   // mppi_chain_config.clamp_mode
+};
+// np.clip in fp64: an operand comes back untouched (a NaN u too)
+__host__ __device__ __forceinline__ double clamp_u(double u, double lo, double hi) { return u < lo ? lo : (u > hi ? hi : u); }
+// the fp32 clip: v_med3_f32 (lo <= hi is guaranteed by mppi_chain_ctx_create), no canonicalising v_max / v_min
+__device__ __forceinline__ float clamp_v(float v, float lo, float hi) { return __builtin_amdgcn_fmed3f(v, lo, hi); }
+// entry d (a lane value) of a by-value table, as selects over its N compile-time entries (no dynamic index
+// into the kernel argument)
+template <int N, class T>
+__device__ __forceinline__ T pick(const T (&tab)[kCMax], int d) {
+    T r = tab[0];
+#pragma unroll
+    for (int e = 1; e < N; ++e) r = d == e ? tab[e] : r;
+    return r;
+}
+
 using CScratch = MergeScratch<kCMaxVals>;
 
 // The dynamics / cost constants, packed (floats, pairs 8-byte aligned).  The
@@ -96,6 +125,11 @@ enum : int {
 };
 static_assert(kDynFloats == kCDyn, "dyn layout");
 constexpr int kDynF64Off = (kCDyn + 1) & ~1;   // floats before the fp64 copy of the constants (8-B aligned)
+// behind the fp64 copy: the fp32 torque limits, v_lo[kCMax] then v_hi[kCMax] (ChainClampK's), for the one-lane-
+// per-sample CLAMP rollout, which reads them per step like the constants above (at n = 7 that kernel has no
+// registers left to hold them across the horizon: held in VGPRs they spilled 30 to scratch)
+constexpr int kDynLimOff = kDynF64Off + 2 * kCDyn;
+constexpr int kDynBlockFloats = kDynLimOff + 2 * kCMax;
 
 template <class F>   // F: const float (generic, kernel argument) or cfloat (constant address space)
 struct Dyn {
@@ -472,10 +506,22 @@ __device__ __forceinline__ void chain_nominal_prefetch(const ChainStep* s, int T
 // min(A5, max(A4, B0), max(A3, B1), max(A2, B2)) (the k-th smallest of two sorted lists is the least
 // max(A_i, B_j) over i + j = k).  80 min / max for the four windows against 4 x 58 with median10, and one
 // pass of the workgroup instead of four; the same element is selected, so the same bits.
-template <int N>
-__device__ __forceinline__ void chain_update_block(ChainStep* nxt, const ChainConst& c, CScratch& sm, const double (&u4)[kMedRun]) {
+//
+// CLAMP: the kernel was built for torque limits; cl.mode == 2 then clips the updated nominal in fp64 as it is
+// written to sm.unew (_g(u[t-1]) over the optimal-trajectory loop, control.py:132-134, clips the whole updated
+// u in place), so u_first, the shifted rows, their a_t and the fp32 ua rows all come from clipped values.
+template <int N, bool CLAMP>
+__device__ __forceinline__ void chain_update_block(ChainStep* nxt, const ChainConst& c, CScratch& sm, const double (&u4)[kMedRun],
+                                                   const ChainClampK& cl) {
     const int tid = threadIdx.x, T = c.T;
     const int q = tid / N, d = tid - q * N, t0 = kMedRun * q;
+    bool clampu = false;
+    double ulo = 0.0, uhi = 0.0;
+    if constexpr (CLAMP) {
+        clampu = cl.mode == 2;
+        ulo = pick<N>(cl.u_lo, d);
+        uhi = pick<N>(cl.u_hi, d);
+    }
     if (t0 < T) {
         double e[13];   // t0 - 5 .. t0 + 7, reflected at both ends (T >= 5: one reflection)
 #pragma unroll
@@ -499,7 +545,9 @@ __device__ __forceinline__ void chain_update_block(ChainStep* nxt, const ChainCo
             CX(B, 0, 1) CX(B, 1, 2) CX(B, 0, 1)
             const double med = min_raw_f64(min_raw_f64(A[5], max_raw_f64(A[4], B[0])),
                                            min_raw_f64(max_raw_f64(A[3], B[1]), max_raw_f64(A[2], B[2])));
-            if (t0 + j < T) sm.unew[(t0 + j) * N + d] = u4[j] + med;
+            double un = u4[j] + med;
+            if (clampu) un = clamp_u(un, ulo, uhi);
+            if (t0 + j < T) sm.unew[(t0 + j) * N + d] = un;
         }
 #undef CX
     }
@@ -539,10 +587,11 @@ __device__ __forceinline__ void chain_update_block(ChainStep* nxt, const ChainCo
 struct alignas(16) WinRowD {
     double x, y, d1, d2;
 };
-template <int N>
+// CLAMP: every sampled control is clipped in fp64 against the fp64 limits (cl.u_lo, cl.u_hi).
+template <int N, bool CLAMP>
 __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const ChainStep* st, cdouble* kd,
                                                     const float* noise, int k, float exf, WinRowD* s_wind,
-                                                    int* slots) {
+                                                    int* slots, const ChainClampK& cl) {
     const int tid = threadIdx.x, K = c.K_local, T = c.T;
     if (tid < kSlots) {
         const double* r = st->wind[tid];
@@ -563,6 +612,7 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
 #pragma unroll
         for (int d = 0; d < N; ++d) {
             v[d] = exf != 0.f ? cu[t * kCMax + d] + (double)nx[d] : (double)nx[d];   // control.py:99-101
+            if constexpr (CLAMP) v[d] = clamp_u(v[d], cl.u_lo[d], cl.u_hi[d]);         // _g, control.py:104
             g = fma(ca[t * kCMax + d], v[d], g);                                      // control.py:106
         }
         const int tn = t + 1 < T ? t + 1 : t;
@@ -661,10 +711,14 @@ __device__ __forceinline__ float elem(f32x2 v) {
 //   steps ahead; the per-step constants from a 2-deep register ring.
 // The stage cost's four terms go to two lanes, two apiece (lane 0 has both joint
 // rates of the cost in its own pair), so it needs no broadcast.
-template <int N>
+// CLAMP: the lane's pair of sampled controls is clipped (v_med3_f32) against its pair of fp32 limits, held in
+// four VGPRs for the whole horizon (they differ by lane, so neither can be a scalar operand), before the pad
+// factor: the pad link of an odd chain stays exactly 0 whatever the limits.
+template <int N, bool CLAMP>
 __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const ChainStep* st, const float* dyn,
                                                    const float* noise, int k, float exf, float4* s_ua4,
-                                                   float4* s_win, int* slots, unsigned long long* dbg) {
+                                                   float4* s_win, int* slots, unsigned long long* dbg,
+                                                   const ChainClampK& cl) {
     static_assert(N <= 8, "four link pairs");
     // the column after which the search is placed: after 2 / 3 / 4 / 5 / 6 measured 77.0 / 76.6 / 77.6 / 75.3 /
     // 77.3 us at K = 16384 (one process, profiles/r13/chain_quad_search_at_ab.txt)
@@ -684,6 +738,14 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
     // theta_dot pair gives q_dot_1, q_dot_2), lane 1 the position terms; lanes 2, 3 weigh theirs by 0
     const bool l0 = sub == 0;
     const f32x2 pad = {a0 < N ? 1.f : 0.f, a1 < N ? 1.f : 0.f};
+    f32x2 vlo = {0.f, 0.f}, vhi = {0.f, 0.f};   // CLAMP: the limits of links (a0, a1); -inf / +inf past the chain
+    if constexpr (CLAMP) {
+        const bool b0 = sub & 1, b1 = sub & 2;
+        vlo = b1 ? (b0 ? f32x2{cl.v_lo[6], cl.v_lo[7]} : f32x2{cl.v_lo[4], cl.v_lo[5]})
+                 : (b0 ? f32x2{cl.v_lo[2], cl.v_lo[3]} : f32x2{cl.v_lo[0], cl.v_lo[1]});
+        vhi = b1 ? (b0 ? f32x2{cl.v_hi[6], cl.v_hi[7]} : f32x2{cl.v_hi[4], cl.v_hi[5]})
+                 : (b0 ? f32x2{cl.v_hi[2], cl.v_hi[3]} : f32x2{cl.v_hi[0], cl.v_hi[1]});
+    }
     const f32x2 l2 = {dyn[kOffL + a0], dyn[kOffL + a1]}, nu2 = {dyn[kOffNu + a0], dyn[kOffNu + a1]};
     const f32x2 damp2 = {dyn[kOffDamp + a0], dyn[kOffDamp + a1]}, fk2 = {dyn[kOffFk + a0], dyn[kOffFk + a1]};
     const float dt = dyn[kOffDt], g = dyn[kOffG];
@@ -765,7 +827,9 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
         f32x2 nz = ring[slot];
         f32x4 ua = {uar[slot].x, uar[slot].y, uar[slot].z, uar[slot].w};
         asm volatile("" : "+v"(nz), "+v"(ua));
-        const f32x2 v = __builtin_elementwise_fma(splat(exf), f32x2{ua.x, ua.y}, nz) * pad;  // control.py:99-101
+        f32x2 v = __builtin_elementwise_fma(splat(exf), f32x2{ua.x, ua.y}, nz);              // control.py:99-101
+        if constexpr (CLAMP) v = f32x2{clamp_v(v.x, vlo.x, vhi.x), clamp_v(v.y, vlo.y, vhi.y)};  // _g, control.py:104
+        v = v * pad;
         G2 = __builtin_elementwise_fma(f32x2{ua.z, ua.w}, v, G2);                          // control.py:106
         ring[slot] = nrow(t + kQPF);
         uar[slot] = s_ua4[(t + kQPF) * 4 + sub];
@@ -894,18 +958,22 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
 // POLL / counter: the hand-off form of the partial rows (handoff_merge in mppi_device.h, shared with rollout_kernel).
 // SLOTS (debug instances, mppi_chain_debug_slots): dbg receives the window slot
 // each sample picked at each step, int32 [k][t].
-template <int N, bool POLL, bool F64, int LPS, bool SLOTS = false>
+// CLAMP: the sampled controls are clipped to the torque limits cl (clamp_mode != 0) and, with cl.mode == 2, so
+// is the fused update's nominal; the CLAMP = false instantiations never read cl.
+template <int N, bool POLL, bool F64, int LPS, bool SLOTS = false, bool CLAMP = false>
 __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) void chain_rollout_kernel(
     const ChainConst c, const ChainStep* __restrict__ st, const float* __restrict__ dyn,
     const float* __restrict__ noise, double* __restrict__ S_out, double* __restrict__ slab, double* __restrict__ gslab,
     unsigned* __restrict__ counters, double* __restrict__ partial_out, double* __restrict__ w_eps_out,
     ChainStep* __restrict__ nxt, unsigned flags, const XDesc xd, unsigned* __restrict__ epoch, unsigned* __restrict__ tmo,
-    unsigned long long* __restrict__ runmin, unsigned long long* __restrict__ dbg) {
+    unsigned long long* __restrict__ runmin, unsigned long long* __restrict__ dbg, const ChainClampK cl) {
     static_assert(N <= kCMax && N >= 2, "links");
+    static_assert(!(SLOTS && CLAMP), "the slot-recording instances are unclamped");
     __shared__ float4 s_win[kSlots];
     __shared__ KeyPair s_keys[kKeyPairs];
     __shared__ WinRowD s_wind[F64 ? kSlots : 1];
     __shared__ float4 s_ua4[LPS == 4 ? (kMaxT + kQPF) * 4 : 1];
+    __shared__ float s_vhi[CLAMP && !F64 && LPS == 1 ? kCMax : 1];   // the upper fp32 limits (one lane per sample)
     __shared__ double s_redd[kCT / 64];
     __shared__ int s_cnt[kCT / 64];
     __shared__ int s_k[kCT];
@@ -934,15 +1002,21 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // poll tags are never 0 (fresh memory)
     unsigned tag_v = POLL ? __hip_atomic_load(epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u : 0u;
     if (POLL && tag_v == 0u) tag_v = 1u;
+    // the one-lane-per-sample fp32 CLAMP kernel reads the nominal only when it updates it: at n = 7 it has no
+    // registers to hold the prefetch across the horizon (the eight went to scratch)
+    constexpr bool kLateNominal = CLAMP && !F64 && LPS == 1;
     double u_cur[kMedRun];
-    chain_nominal_prefetch<N>(st, T, flags & MPPI_FLAG_FUSED_UPDATE, u_cur);
+    if constexpr (!kLateNominal) chain_nominal_prefetch<N>(st, T, flags & MPPI_FLAG_FUSED_UPDATE, u_cur);
     double S = 0.0;
     if constexpr (F64) {
-        S = chain_horizon_f64<N>(c, st, (cdouble*)(dyn + kDynF64Off), noise, k, exf, s_wind, slots);
+        S = chain_horizon_f64<N, CLAMP>(c, st, (cdouble*)(dyn + kDynF64Off), noise, k, exf, s_wind, slots, cl);
     } else if constexpr (LPS == 4) {
-        S = chain_horizon_q4<N>(c, st, dyn, noise, k, exf, s_ua4, s_win, slots, dbg);
+        S = chain_horizon_q4<N, CLAMP>(c, st, dyn, noise, k, exf, s_ua4, s_win, slots, dbg, cl);
     } else {
     if (tid < kSlots) s_win[tid] = st->win[tid];
+    if constexpr (CLAMP) {
+        if (tid < kCMax) s_vhi[tid] = dyn[kDynLimOff + kCMax + tid];
+    }
     // window keys in LDS (broadcast reads): the 90 key registers would cost the
     // chain kernel its second wave per SIMD; precise keys: the config-5 start
     // pose sits on a waypoint
@@ -982,6 +1056,9 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int d = 0; d < N; ++d) {
             v[d] = fmaf(exf, uring[i % kCPU][d], ring[i % kCPF][d]);   // u_t + eps or eps
+            // _g, control.py:104: v_med3_f32 takes one scalar operand, the lower limit (read like the other
+            // constants); the upper one comes from LDS into a VGPR that lives for this instruction only
+            if constexpr (CLAMP) v[d] = clamp_v(v[d], kd.p[kDynLimOff + d], s_vhi[d]);
             g = fmaf(uring[i % kCPU][N + d], v[d], g);                 // (gamma u_t^T Sigma^-1) v, control.py:106
         }
 #pragma unroll
@@ -1131,15 +1208,17 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned xtag = (flags & MPPI_FLAG_EXCHANGE)
                               ? exchange_send_merge<kCT, kCMaxCh>(xd, geo, c.inv_lambda, sm, w_eps_out, tmo) : 0u;
     if (tid == 0 && w_eps_out) w_eps_out[nval] = sm.eta;   // the weights' spread (mppi_chain_last_eta)
-    if (flags & MPPI_FLAG_FUSED_UPDATE) chain_update_block<N>(nxt, c, sm, u_cur);
+    if constexpr (kLateNominal) chain_nominal_prefetch<N>(st, T, flags & MPPI_FLAG_FUSED_UPDATE, u_cur);
+    if (flags & MPPI_FLAG_FUSED_UPDATE) chain_update_block<N, CLAMP>(nxt, c, sm, u_cur, cl);
     if (flags & MPPI_FLAG_EXCHANGE) exchange_verdict<kCT>(xd, geo, xtag, tmo);
     STAMP(7, NOW());
 }
 
 // Merge of the all-gathered per-device rows (multi-GPU), plus the fused update.
-template <int N>
+template <int N, bool CLAMP>
 __global__ __launch_bounds__(kCT) void chain_merge_kernel(const ChainConst c, const ChainStep* cur, const double* parts,
-                                                          int n, double* w_eps_out, ChainStep* nxt, unsigned flags) {
+                                                          int n, double* w_eps_out, ChainStep* nxt, unsigned flags,
+                                                          const ChainClampK cl) {
     __shared__ CScratch sm;
     const int tid = threadIdx.x, T = c.T;
     double u_cur[kMedRun];
@@ -1149,19 +1228,21 @@ __global__ __launch_bounds__(kCT) void chain_merge_kernel(const ChainConst c, co
     merge_rows_block<kCT, kCMaxCh, true, false>(r, 0, n, geo, c.inv_lambda, sm, nullptr, 0, nullptr, w_eps_out, 0u,
                                                 nullptr);
     if (tid == 0 && w_eps_out) w_eps_out[T * N] = sm.eta;
-    if (flags & MPPI_FLAG_FUSED_UPDATE) chain_update_block<N>(nxt, c, sm, u_cur);
+    if (flags & MPPI_FLAG_FUSED_UPDATE) chain_update_block<N, CLAMP>(nxt, c, sm, u_cur, cl);
 }
 
 // Trajectory re-roll (control.py:129-145 with the chain): control(t) =
 // base[(t-1) mod T] (+ eps); out[k][t][2N] = (q, dq) after step t.  As in
 // traj_kernel, the states of kChainTB steps go through an LDS tile and each
 // flush writes every sample's kChainTB * 2N floats as one contiguous run.
+// CLAMP (clamp_mode >= 1): the control fed to the dynamics is clipped, _g(u[t-1]) / _g(v[k, t-1]) of
+// control.py:133,143.
 constexpr int kChainTB = 2;
-template <int N, bool NOISE>
+template <int N, bool NOISE, bool CLAMP>
 __global__ __launch_bounds__(kCT) void chain_traj_kernel(const ChainConst c, const ChainStep* __restrict__ st,
                                                          const float* __restrict__ base,
                                                          const float* __restrict__ noise, int Kn,
-                                                         float* __restrict__ out) {
+                                                         float* __restrict__ out, const ChainClampK cl) {
     constexpr int W = 2 * N;   // floats per state
     __shared__ float tile[kChainTB][W][kCT];
     const int tid = threadIdx.x;
@@ -1198,6 +1279,7 @@ __global__ __launch_bounds__(kCT) void chain_traj_kernel(const ChainConst c, con
             for (int d = 0; d < N; ++d) {
                 v[d] = base[ti * N + d];
                 if (NOISE) v[d] = fmaf(exf, v[d], cur[j][d]);
+                if constexpr (CLAMP) v[d] = clamp_v(v[d], cl.v_lo[d], cl.v_hi[d]);
             }
             x.step(v, DynArg{c.dyn});
 #pragma unroll
@@ -1270,6 +1352,7 @@ struct mppi_chain_ctx {
     int nblocks = 0;
     mppi_host::Handoff hand;       // hand-off form, its buffers and the time-out words
     ChainConst kc;
+    ChainClampK ck{};              // torque limits (mode 0: none)
     mppi_host::DevBuf<ChainStep> d_step;      // [2] ping-pong
     int cur = 0;
     mppi_host::PinnedBuf<ChainStep> h_step;   // pinned staging
@@ -1302,21 +1385,21 @@ namespace {
 using mppi_host::fail;
 using mppi_host::launch_check;
 
-template <int N, bool P, bool F64, int LPS>
+template <int N, bool P, bool F64, int LPS, bool CL>
 void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise, double* S, double* part, ChainStep* nxt,
                     unsigned flags, int* slots = nullptr) {
     const mppi_host::Handoff& h = c->hand;
-    if (slots) {   // the debug instance: identical arithmetic, plus the slot stores
-        if constexpr (N == kCDebugN)
+    if (slots) {   // the debug instance: identical arithmetic, plus the slot stores (unclamped contexts only)
+        if constexpr (N == kCDebugN && !CL)
             hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, true>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc,
                                cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags,
                                c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin,
-                               reinterpret_cast<unsigned long long*>(slots));
+                               reinterpret_cast<unsigned long long*>(slots), c->ck);
         return;
     }
-    hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc, cur, c->d_dyn,
-                       noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags, c->ex.xd, h.d_epoch,
-                       h.h_tmo.dev, c->d_runmin, c->d_dbg);
+    hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, false, CL>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc,
+                       cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags, c->ex.xd,
+                       h.d_epoch, h.h_tmo.dev, c->d_runmin, c->d_dbg, c->ck);
 }
 
 // the link counts with an instantiated kernel: f(N) for N = n as an integral constant
@@ -1325,17 +1408,19 @@ void with_links(int n, F&& f) {
     mppi_host::with_value<2, 3, 4, 5, 6, 7>(n, f);
 }
 
-// The instantiated rollout kernels: links x POLL x (fp64 at one lane per sample, fp32 at one or four).  Calls
-// f(n, poll, f64, lps), the context's instance as integral constants, in the hand-off form `poll`.
+// The instantiated rollout kernels: links x POLL x (fp64 at one lane per sample, fp32 at one or four) x CLAMP.
+// Calls f(n, poll, f64, lps, clamp), the context's instance as integral constants, in the hand-off form `poll`.
 template <class F>
 void with_rollout(const mppi_chain_ctx* c, bool poll, F&& f) {
     using L1 = std::integral_constant<int, 1>;
     using L4 = std::integral_constant<int, 4>;
     with_links(c->n, [&](auto n) {
         mppi_host::with_bool(poll, [&](auto p) {
-            if (c->f64) f(n, p, std::true_type{}, L1{});
-            else if (c->lps == 4) f(n, p, std::false_type{}, L4{});
-            else f(n, p, std::false_type{}, L1{});
+            mppi_host::with_bool(c->ck.mode != 0, [&](auto cl) {
+                if (c->f64) f(n, p, std::true_type{}, L1{}, cl);
+                else if (c->lps == 4) f(n, p, std::false_type{}, L4{}, cl);
+                else f(n, p, std::false_type{}, L1{}, cl);
+            });
         });
     });
 }
@@ -1390,8 +1475,9 @@ int alloc(mppi_chain_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     int ncu = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-    with_rollout(c, true, [&](auto n, auto p, auto f64, auto lps) {   // always of the POLL form
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps>, kCT, 0);
+    with_rollout(c, true, [&](auto n, auto p, auto f64, auto lps, auto cl) {   // always of the POLL form
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl>, kCT, 0);
     });
     // behind the counters: the per-CU ticket words of the issue fairness (mppi_device.h)
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + c->cfg.T * c->n, kCuSlots)) return rc;
@@ -1403,7 +1489,9 @@ int alloc(mppi_chain_ctx* c) {
     HIP_TRY(hipMemset(c->d_runmin, 0xFF, 256));
     if (int rc = c->d_weps.alloc_zeroed(kCMaxVals + 1)) return rc;
     if (int rc = c->d_base.alloc(kCMaxVals)) return rc;
-    if (int rc = c->d_dyn.alloc(kDynF64Off + 2 * kCDyn)) return rc;   // the fp32 table, then h_dynd
+    if (int rc = c->d_dyn.alloc(kDynBlockFloats)) return rc;   // the fp32 table, then h_dynd, then the fp32 limits
+    static_assert(offsetof(ChainClampK, v_hi) == offsetof(ChainClampK, v_lo) + kCMax * sizeof(float), "v_lo, then v_hi");
+    HIP_TRY(hipMemcpy(c->d_dyn + kDynLimOff, c->ck.v_lo, 2 * kCMax * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_dyn + kDynF64Off, c->h_dynd, sizeof(c->h_dynd), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_dyn, c->kc.dyn, sizeof(c->kc.dyn), hipMemcpyHostToDevice));
     if (int rc = c->h_step.alloc(1)) return rc;
@@ -1436,6 +1524,13 @@ int mppi_chain_ctx_create(const mppi_chain_config* cfg, int device, void* stream
     if (cfg->T < 1 || cfg->T > MPPI_MAX_T) return fail(MPPI_E_ARG, "T must be in [1, 128]");
     if (cfg->T * n + 1 > kCMaxCh * kCT) return fail(MPPI_E_ARG, "T * n too large");
     if (cfg->precision != 0 && cfg->precision != 1) return fail(MPPI_E_ARG, "precision must be 0 (fp32) or 1 (fp64)");
+    if (cfg->clamp_mode < 0 || cfg->clamp_mode > 2) return fail(MPPI_E_ARG, "clamp_mode must be 0, 1 or 2");
+    if (cfg->clamp_mode > 0)
+        for (int d = 0; d < n; ++d) {
+            if (isnan(cfg->u_min[d])) return fail(MPPI_E_ARG, "u_min: a limit is NaN (use -inf for no limit)");
+            if (isnan(cfg->u_max[d])) return fail(MPPI_E_ARG, "u_max: a limit is NaN (use +inf for no limit)");
+            if (cfg->u_min[d] > cfg->u_max[d]) return fail(MPPI_E_ARG, "u_min[d] > u_max[d]: the limits are crossed");
+        }
     if (int rc = mppi_host::check_sample_geometry(cfg->K_local, cfg->K_total, cfg->k_offset)) return rc;
     if ((long long)cfg->K_local * cfg->T * n >= (1LL << 31)) return fail(MPPI_E_ARG, "too many samples");
     // Sigma: symmetric positive definite (Cholesky), inverse for the control cost
@@ -1511,6 +1606,17 @@ int mppi_chain_ctx_create(const mppi_chain_config* cfg, int device, void* stream
     dynd[kOffG] = P.g;
     for (int i = 0; i < kCDyn; ++i) k.dyn[i] = (float)dynd[i];
     for (int i = 0; i < n * n; ++i) k.sig_inv[i] = Si[i];
+    ChainClampK& ck = c->ck;
+    ck.mode = cfg->clamp_mode;
+    for (int d = 0; d < kCMax; ++d) {
+        // without limits the fields are never read; entries past the chain (the quad's pad link) never clip;
+        // the fp32 rollouts clip against the limits rounded to nearest
+        const bool on = cfg->clamp_mode && d < n;
+        ck.u_lo[d] = on ? cfg->u_min[d] : -INFINITY;
+        ck.u_hi[d] = on ? cfg->u_max[d] : INFINITY;
+        ck.v_lo[d] = (float)ck.u_lo[d];
+        ck.v_hi[d] = (float)ck.u_hi[d];
+    }
 
     for (int i = 0; i < n; ++i)
         for (int j = 0; j <= i; ++j) c->chol.L[i * kCMax + j] = (float)(Lc[i][j] * kBoxMullerScale);   // box_muller's constant
@@ -1599,8 +1705,8 @@ int chain_rollout(mppi_chain_ctx* c, const float* noise_dev, double* S_dev, doub
     }
     const ChainStep* cur = c->d_step + c->cur;
     ChainStep* nxt = c->d_step + (c->cur ^ 1);
-    with_rollout(c, c->hand.poll, [&](auto n, auto p, auto f64, auto lps) {
-        launch_rollout<n, p, f64, lps>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots);
+    with_rollout(c, c->hand.poll, [&](auto n, auto p, auto f64, auto lps, auto cl) {
+        launch_rollout<n, p, f64, lps, cl>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots);
     });
     if (int rc = launch_check("chain_rollout_kernel")) return rc;
     note_update(c, flags);
@@ -1625,6 +1731,7 @@ int mppi_chain_rollout(mppi_chain_ctx* c, const float* noise_dev, double* S_dev,
 int mppi_chain_debug_slots(mppi_chain_ctx* c, const float* noise_dev, double* S_dev, int* slots_dev) {
     if (!c || !noise_dev || !slots_dev) return fail(MPPI_E_ARG, "null argument");
     if (c->n != kCDebugN) return fail(MPPI_E_ARG, "slot recording is built for the 7-link chain only");
+    if (c->ck.mode != 0) return fail(MPPI_E_ARG, "slot recording is built without torque limits (clamp_mode 0 only)");
     return chain_rollout(c, noise_dev, S_dev, nullptr, 0u, slots_dev);
 }
 
@@ -1647,8 +1754,10 @@ int mppi_chain_merge_partials(mppi_chain_ctx* c, const double* partials_dev, int
     const ChainStep* cur = c->d_step + c->cur;
     ChainStep* nxt = c->d_step + (c->cur ^ 1);
     with_links(c->n, [&](auto n) {
-        hipLaunchKernelGGL(chain_merge_kernel<n>, dim3(1), dim3(kCT), 0, c->stream, c->kc, cur, partials_dev, nparts,
-                           c->d_weps, nxt, flags);
+        mppi_host::with_bool(c->ck.mode != 0, [&](auto cl) {
+            hipLaunchKernelGGL((chain_merge_kernel<n, cl>), dim3(1), dim3(kCT), 0, c->stream, c->kc, cur, partials_dev,
+                               nparts, c->d_weps, nxt, flags, c->ck);
+        });
     });
     if (int rc = launch_check("chain_merge_kernel")) return rc;
     note_update(c, flags);
@@ -1688,15 +1797,17 @@ namespace {
 // control.py:129-134 for the chain in fp64 on the host: x_{t+1} = F(x_t, u_new[t - 1]) (u_new[-1] at t = 0),
 // the same ChainStateD step as the fp64 rollout.  One sequential trajectory: the host's fp64 is ~5x the
 // device's single lane here (~1.7 us per step of dependent VALU on one wave).
+// lim: the torque limits (u_lo[kCMax], u_hi[kCMax]) when the context has them: the control is clipped as it is
+// fed to the step (_g(u[t-1]), control.py:133), u_new itself untouched; null: none.
 template <int N>
 __attribute__((always_inline)) inline void chain_traj_body(const double* kd, const double* x0, const double* u_new,
-                                                           int T, double* out) {
+                                                           int T, double* out, const double* lim) {
     ChainStateD<N> x;
     x.load(x0);
     for (int t = 0; t < T; ++t) {
         const double* ut = u_new + (size_t)N * (t == 0 ? T - 1 : t - 1);
         double v[N];
-        for (int d = 0; d < N; ++d) v[d] = ut[d];
+        for (int d = 0; d < N; ++d) v[d] = lim ? clamp_u(ut[d], lim[d], lim[kCMax + d]) : ut[d];
         x.step(v, kd);
         for (int a = 0; a < N; ++a) {
             out[(size_t)t * 2 * N + a] = x.q[a];
@@ -1710,15 +1821,15 @@ __attribute__((always_inline)) inline void chain_traj_body(const double* kd, con
 // bits (MPPI_HOST_FMA=0 forces the baseline instance; tests/test_gpu_chain.py compares the two).
 template <int N>
 __attribute__((target("fma"))) void chain_traj_host_fma(const double* kd, const double* x0, const double* u_new,
-                                                        int T, double* out) {
-    chain_traj_body<N>(kd, x0, u_new, T, out);
+                                                        int T, double* out, const double* lim) {
+    chain_traj_body<N>(kd, x0, u_new, T, out, lim);
 }
 template <int N>
-void chain_traj_host(const double* kd, const double* x0, const double* u_new, int T, double* out) {
+void chain_traj_host(const double* kd, const double* x0, const double* u_new, int T, double* out, const double* lim) {
     static const bool hw_fma = __builtin_cpu_supports("fma");
     const char* force = getenv("MPPI_HOST_FMA");
-    if (hw_fma && !(force && force[0] == '0')) chain_traj_host_fma<N>(kd, x0, u_new, T, out);
-    else chain_traj_body<N>(kd, x0, u_new, T, out);
+    if (hw_fma && !(force && force[0] == '0')) chain_traj_host_fma<N>(kd, x0, u_new, T, out, lim);
+    else chain_traj_body<N>(kd, x0, u_new, T, out, lim);
 }
 }  // namespace
 
@@ -1754,7 +1865,9 @@ int mppi_chain_wait_outputs(mppi_chain_ctx* c, const double* x0, double* u_out, 
 
 int mppi_chain_optimal_traj_host(mppi_chain_ctx* c, const double* x0, const double* u_new, double* traj_out) {
     if (!c || !x0 || !u_new || !traj_out) return fail(MPPI_E_ARG, "null argument");
-    with_links(c->n, [&](auto n) { chain_traj_host<n>(c->h_dynd, x0, u_new, c->cfg.T, traj_out); });
+    static_assert(offsetof(ChainClampK, u_hi) == offsetof(ChainClampK, u_lo) + kCMax * sizeof(double), "u_lo, then u_hi");
+    const double* lim = c->ck.mode != 0 ? c->ck.u_lo : nullptr;   // clamp_mode >= 1: the control is clipped in fp64
+    with_links(c->n, [&](auto n) { chain_traj_host<n>(c->h_dynd, x0, u_new, c->cfg.T, traj_out, lim); });
     return MPPI_OK;
 }
 
@@ -1775,8 +1888,10 @@ int mppi_chain_rollout_traj(mppi_chain_ctx* c, const double* base_u, const float
     const int blocks = (K + kCT - 1) / kCT;
     with_links(n, [&](auto nl) {
         mppi_host::with_bool(noise_dev != nullptr, [&](auto noisy) {
-            hipLaunchKernelGGL((chain_traj_kernel<nl, noisy>), dim3(blocks), dim3(kCT), 0, c->stream, c->kc, cur,
-                               c->d_base, noise_dev, K, out_dev);
+            mppi_host::with_bool(c->ck.mode != 0, [&](auto cl) {
+                hipLaunchKernelGGL((chain_traj_kernel<nl, noisy, cl>), dim3(blocks), dim3(kCT), 0, c->stream, c->kc, cur,
+                                   c->d_base, noise_dev, K, out_dev, c->ck);
+            });
         });
     });
     return launch_check("chain_traj_kernel");

@@ -68,6 +68,27 @@ class _Engine:
         self._ctx = ctx
         self.partial_len = 2 + self.dim_u * self.T
 
+    # -- torque limits ------------------------------------------------------
+    @staticmethod
+    def clamp_mode(u_min, u_max, clamp_nominal: bool) -> int:
+        """clamp_mode of either config: 0 without limits, 2 with them, 1 with them and clamp_nominal off."""
+        if u_min is None and u_max is None:
+            return 0
+        return 2 if clamp_nominal else 1
+
+    def _set_limits(self, cfg, dim_u: int, u_min, u_max, clamp_nominal: bool) -> None:
+        """clamp_mode / u_min / u_max of `cfg` (either config struct) from limits given as a scalar or one value
+        per control component (None: no limit on that side), and self.u_min / self.u_max: the (dim_u,) fp64
+        limits the context holds, or None without limits."""
+        cfg.clamp_mode = self.clamp_mode(u_min, u_max, clamp_nominal)
+        if cfg.clamp_mode:
+            lo = np.broadcast_to(np.asarray(-np.inf if u_min is None else u_min, dtype=np.float64), (dim_u,))
+            hi = np.broadcast_to(np.asarray(np.inf if u_max is None else u_max, dtype=np.float64), (dim_u,))
+            for d in range(dim_u):
+                cfg.u_min[d], cfg.u_max[d] = float(lo[d]), float(hi[d])
+        self.u_min = None if not cfg.clamp_mode else np.array(cfg.u_min[:dim_u])
+        self.u_max = None if not cfg.clamp_mode else np.array(cfg.u_max[:dim_u])
+
     # -- lifetime -----------------------------------------------------------
     def close(self) -> None:
         if getattr(self, "_ctx", None):
@@ -290,14 +311,7 @@ class RolloutEngine(_Engine):
         and with clamp_nominal (the reference with visualize_optimal_traj) the fused update clips the nominal
         too.  The context rejects NaN limits and u_min > u_max (ValueError)."""
         cfg = N.ConfigC()
-        cfg.clamp_mode = self.clamp_mode(u_min, u_max, clamp_nominal)
-        if cfg.clamp_mode:
-            lo = np.broadcast_to(np.asarray(-np.inf if u_min is None else u_min, dtype=np.float64), (2,))
-            hi = np.broadcast_to(np.asarray(np.inf if u_max is None else u_max, dtype=np.float64), (2,))
-            for d in range(2):
-                cfg.u_min[d], cfg.u_max[d] = float(lo[d]), float(hi[d])
-        self.u_min = None if not cfg.clamp_mode else np.array(cfg.u_min)
-        self.u_max = None if not cfg.clamp_mode else np.array(cfg.u_max)
+        self._set_limits(cfg, 2, u_min, u_max, clamp_nominal)
         cfg.delta_t = float(delta_t)
         cfg.param_lambda = float(param_lambda)
         cfg.param_alpha = float(param_alpha)
@@ -323,13 +337,6 @@ class RolloutEngine(_Engine):
         N.check(self._lib.mppi_ctx_handoff(self._ctx, C.byref(poll)), "mppi_ctx_handoff")
         # in-launch hand-off of the workgroup partials: "poll" (tagged granules) or "counter"
         self.handoff = "poll" if poll.value else "counter"
-
-    @staticmethod
-    def clamp_mode(u_min, u_max, clamp_nominal: bool) -> int:
-        """mppi_config.clamp_mode: 0 without limits, 2 with them, 1 with them and clamp_nominal off."""
-        if u_min is None and u_max is None:
-            return 0
-        return 2 if clamp_nominal else 1
 
     def merge(self, partials: torch.Tensor, n: int, fused_update: bool = False, host_out: bool = False) -> None:
         super().merge(partials, n, fused_update, N.MPPI_FLAG_HOST_OUT if host_out else 0)   # host_out: the arm only
