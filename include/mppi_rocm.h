@@ -312,6 +312,44 @@ int mppi_noise_philox(mppi_ctx *ctx, unsigned long long seed, unsigned long long
  * invalid; it cannot happen while the grid is co-resident). */
 int mppi_sync(mppi_ctx *ctx);
 
+/* Workspace obstacles: a collision cost on both links of the arm.  Up to
+ * MPPI_MAX_OBSTACLES discs (cx, cy, r) in the plane of the arm, discs[n][3]
+ * row-major, and one cost >= 0.  A state collides when either link touches a
+ * disc; a link is a zero-thickness segment in the cost's kinematics (fk_l1,
+ * fk_l2, base at the origin, as the stage cost computes x and y,
+ * control.py:178-179): link 1 from (0, 0) to e = fk_l1 (cos q1, sin q1), link 2
+ * from e to e + fk_l2 (cos(q1 + q2), sin(q1 + q2)); "touches": the distance from
+ * the centre to the segment, the projection clipped to it, is < r (a margin or
+ * a link thickness goes into r).  Every step of the horizon whose new state
+ * collides adds `cost` to that sample's S, and the final state adds it once more
+ * as a terminal term: S = S_track + cost * hits, hits in [0, T + 1] — the
+ * reference with _c and _phi (control.py:174-198) returning ... + cost *
+ * collides(x).  Dynamics, weights, weighted noise, filter, update, the
+ * trajectory re-rolls, the exploration split and the torque limits are
+ * untouched.  The test runs in fp32 on the rollout's own (cos, sin) values: a
+ * state within ~4e-6 m of a disc's boundary may fall on either side.
+ *
+ * Takes effect at the next launch of any kind (mppi_rollout, mppi_step_dropin,
+ * the bound tick, a launch with the exchange): the discs are a by-value
+ * argument of that launch, like the observed state, so they may change from
+ * one control step to the next; a captured graph freezes the discs it was
+ * captured with.  n = 0 removes them: the context then launches exactly the
+ * kernels it launched before any were set.  No device call.  MPPI_E_ARG for n
+ * outside 0..MPPI_MAX_OBSTACLES, a NaN or negative r, a non-finite centre, and
+ * a NaN, negative or infinite cost; the discs in effect are then kept.
+ * mppi_config does not carry them: obstacles move between control steps. */
+#define MPPI_MAX_OBSTACLES 8
+int mppi_set_obstacles(mppi_ctx *ctx, int n, const double *discs, double cost);
+
+/* Tests: the collision test of the first K samples at every step as the rollout
+ * evaluates it (the same fp32 dynamics and the same device function) on the
+ * current step inputs, discs and noise_dev ([T][K_local][2] fp32).
+ * mask_dev[K][T] (uint32 device): bit 2j set when link 1 touches disc j, bit
+ * 2j + 1 when link 2 does; dir_dev[K][T][4] (fp32 device): the (cos q1, sin q1,
+ * cos(q1 + q2), sin(q1 + q2)) the test was evaluated on. */
+int mppi_debug_obstacle_hits(mppi_ctx *ctx, const float *noise_dev, int K, unsigned *mask_dev,
+                             float *dir_dev);
+
 /* Diagnostics: in a -DMPPI_STAMPS build the rollout kernel writes a per-workgroup
  * timeline (16 uint64 per workgroup) to dbg_dev; product builds ignore it. */
 int mppi_debug_set_buffer(mppi_ctx *ctx, void *dbg_dev);

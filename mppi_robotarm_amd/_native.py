@@ -27,6 +27,7 @@ MPPI_FLAG_HOST_OUT = 4
 DP = C.POINTER(C.c_double)
 MPPI_IPC_HANDLE_BYTES = 64
 MPPI_MAX_WORLD = 8
+MPPI_MAX_OBSTACLES = 8
 
 # every symbol the header declares (tests check the library exports all of them)
 EXPORTS = (
@@ -38,7 +39,7 @@ EXPORTS = (
     "mppi_dropin_tick_launch", "mppi_dropin_tick_wait",
     "mppi_noise_philox",
     "mppi_sync", "mppi_debug_set_buffer",
-    "mppi_debug_nearest", "mppi_debug_dropin_times",
+    "mppi_debug_nearest", "mppi_debug_dropin_times", "mppi_set_obstacles", "mppi_debug_obstacle_hits",
     "mppi_chain_ctx_create", "mppi_chain_ctx_destroy", "mppi_chain_set_stream", "mppi_chain_ctx_info",
     "mppi_chain_set_step_inputs", "mppi_chain_rollout", "mppi_chain_merge_partials", "mppi_chain_exchange_handle",
     "mppi_chain_exchange_attach",
@@ -173,6 +174,8 @@ def open_library(path: str):
         "mppi_debug_set_buffer": ([vp, vp], C.c_int),
         "mppi_debug_dropin_times": ([vp, dp], C.c_int),
         "mppi_debug_nearest": ([vp, fp, C.c_int, vp, fp], C.c_int),
+        "mppi_set_obstacles": ([vp, C.c_int, dp, C.c_double], C.c_int),
+        "mppi_debug_obstacle_hits": ([vp, fp, C.c_int, vp, fp], C.c_int),
         "mppi_chain_ctx_create": ([C.POINTER(ChainConfigC), C.c_int, vp, C.POINTER(vp)], C.c_int),
         "mppi_chain_ctx_destroy": ([vp], None),
         "mppi_chain_set_stream": ([vp, vp], C.c_int),

@@ -33,6 +33,11 @@ joint: the reference's clamp hook ``_g``, control.py:166-172, switched on —
 the sampled controls are clipped before the dynamics and the control cost, the
 weights still multiply the unclamped noise, and with ``visualize_optimal_traj``
 the updated nominal is clipped too, exactly as ``_g`` clipping in place would),
+``obstacles`` / ``obstacle_cost`` (up to eight discs ``(cx, cy, r)`` that neither
+link may touch: every colliding step of a sample, and its final state once more,
+adds ``obstacle_cost`` to its cost, the reference with ``_c`` and ``_phi``
+returning ``... + obstacle_cost * collides(x)``; plain attributes, re-read on
+every call, so they may move between calls),
 ``process_group`` (shard the samples over the ranks of a
 torch.distributed group), ``exchange`` (with a process group: "auto" = the
 in-launch exchange, one launch per rank per step, when its one-step self-check
@@ -96,6 +101,8 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
             arm: ArmParams | None = None,
             u_min=None,
             u_max=None,
+            obstacles=None,
+            obstacle_cost: float = 1.0e10,
             process_group=None,
             exchange: str = "auto",
             host_update: bool = False,
@@ -130,6 +137,11 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
         self.host_update = host_update  # property: forced, or T < 5 (the device median needs T >= 5)
         self.u_min, self.u_max = u_min, u_max   # properties: torque limits of _g, validated
         self._limits()                          # u_min <= u_max
+        self.obstacles = obstacles              # (n, 3) array-like of discs (cx, cy, r), n <= 8, or None
+        self.obstacle_cost = obstacle_cost      # added to S per colliding step (and once for the final state)
+        self._obst_checked = None               # the last (obstacles bytes, cost) that passed the checks
+        self._okey = None                       # this call's key, for _tick (whose signature tests stub)
+        self._obstacle_key()
         self._bound = None             # what the engine's drop-in tick is bound to (_bind_key)
         self._fast = None              # what the last bound tick checked (calc_control_input's fast test)
 
@@ -177,6 +189,35 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
                                              device=self._engine.device)
             self._xmode = None
         return self._engine
+
+    # ------------------------------------------------------------ obstacles
+    def _obstacle_key(self):
+        """self.obstacles / self.obstacle_cost by value: None without discs, else (the (n, 3) fp64 bytes, the
+        cost), checked (ValueError for a bad shape or value).  Compared on every call, the bound tick's too,
+        so a rebind and an in-place edit are both seen."""
+        if self.obstacles is None:
+            return None
+        try:
+            a = np.array(self.obstacles, dtype=np.float64, ndmin=1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"obstacles: {e}") from None
+        if a.size == 0:
+            return None
+        try:
+            key = (a.shape, a.tobytes(), float(self.obstacle_cost))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"obstacle_cost: {e}") from None
+        if key != self._obst_checked:
+            RolloutEngine.check_obstacles(a, self.obstacle_cost)
+            self._obst_checked = key
+        return key
+
+    def _push_obstacles(self, eng: RolloutEngine, key) -> None:
+        """Give the engine this call's discs unless it holds them already (no device call either way)."""
+        have = eng.obstacles
+        have = (have.shape, have.tobytes(), eng.obstacle_cost) if have.shape[0] else None
+        if key != have:
+            eng.set_obstacles(None if key is None else self.obstacles, self.obstacle_cost)
 
     def _multi_rollout(self, eng: RolloutEngine, S_out, fused: bool) -> None:
         """control.py:81-118 over every rank's shard, the rows merged on every rank:
@@ -230,10 +271,11 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
         self._noise_ready = None
 
     def _calc_control_input(self, observed_x: np.ndarray) -> Tuple[float, np.ndarray]:
+        okey = self._okey = self._obstacle_key()           # ValueError before anything is drawn or moved
         if self._npre is not None and self.noise_source != "numpy":
             self._settle_predraw()                         # (the NumPy path settles it after its checks)
         f = self._fast
-        if (f is not None and f[0] is self.ref_path and f[1] is self.u_prev and f[2] is self.Sigma
+        if (f is not None and f[10] == okey and f[0] is self.ref_path and f[1] is self.u_prev and f[2] is self.Sigma
                 and f[3] is self.stage_cost_weight and f[4] is self.terminal_cost_weight and f[5] is self._engine
                 and f[6] == self._fast_scalars() and f[7] == self.Sigma.tobytes()
                 and f[8] == self.stage_cost_weight.tobytes() and f[9] == self.terminal_cost_weight.tobytes()):
@@ -263,6 +305,7 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
         if key != self._engine_built_for:
             np.linalg.inv(self.Sigma)                      # LinAlgError exactly as control.py:106
         eng = self._get_engine(key)
+        self._push_obstacles(eng, okey)
         if isinstance(epsilon, DeviceDrawn):
             pass                                           # already in self._noise_dev
         elif isinstance(epsilon, hostrng.StdNoise):
@@ -343,6 +386,8 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
         if self._engine is None or key != self._engine_built_for:
             return None                                    # (re)build on the general path (LinAlgError order kept)
         eng = self._engine
+        okey = self._okey                                  # this call's discs (_calc_control_input)
+        self._push_obstacles(eng, okey)
         bkey = (eng, path, u, self.keep_costs, self.visualize_optimal_traj, self.seed, self.l1, self.l2,
                 self._noise_dev)                           # (a NumPy-noise run swaps the noise buffers)
         if self._bound is None or any(a is not b for a, b in zip(bkey, self._bound)):
@@ -361,7 +406,7 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
                for a in (self.Sigma, self.stage_cost_weight, self.terminal_cost_weight)):
             self._fast = (path, u, self.Sigma, self.stage_cost_weight, self.terminal_cost_weight, eng,
                           self._fast_scalars(), self.Sigma.tobytes(), self.stage_cost_weight.tobytes(),
-                          self.terminal_cost_weight.tobytes())
+                          self.terminal_cost_weight.tobytes(), okey)
         return out
 
     def _fast_scalars(self):

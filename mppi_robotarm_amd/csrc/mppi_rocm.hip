@@ -27,6 +27,10 @@
 //    v_med3_f32 per component before the control cost and the dynamics, and the fused update clips the
 //    nominal in fp64 (mode 2).  The limits travel in ClampK, the kernels' last argument, which the other
 //    instantiations never read: they are the code they were without the feature.
+//  * workspace obstacles (mppi_set_obstacles): the OBST instantiations of the rollout kernel test both links
+//    against up to eight discs after every step, on the (cos, sin) pairs the step just produced, count the
+//    colliding steps per sample in an integer and add cost x count to S once, in fp64.  The discs travel in
+//    ObstK, the last argument after ClampK; a context without discs launches the kernels it launched before.
 //  * merge_kernel: the same merge over the all-gathered per-device partials
 //    (multi-GPU), traj_kernel: trajectory re-roll (control.py:129-145),
 //    philox_noise_kernel: counter-based Gaussian noise.
@@ -89,6 +93,17 @@ struct ClampK {
     double u_lo[2], u_hi[2];
     float v_lo[2], v_hi[2];
     int mode;
+};
+
+// Workspace obstacles (mppi_set_obstacles): up to MPPI_MAX_OBSTACLES discs in the plane of the arm, two per
+// register pair (disc 2p in the low half, disc 2p + 1 in the high half; an unused entry has r2 = -1, which no
+// squared distance is below), and the cost of one colliding step.  The last argument of the rollout kernel,
+// after ClampK, read by the OBST instantiations only.  A per-launch input like StepStatic.
+struct ObstK {
+    float cx[MPPI_MAX_OBSTACLES], cy[MPPI_MAX_OBSTACLES];   // centres, fp32
+    float r2[MPPI_MAX_OBSTACLES];                           // r^2 (fp64 product, rounded once)
+    double w;
+    int n;
 };
 
 // One semi-implicit Euler step of _F (control.py:234-263) in closed form:
@@ -175,6 +190,89 @@ __device__ __forceinline__ f32x2 clamp_v(f32x2 v, const DynK& k) {
 }
 
 __device__ __forceinline__ f32x2 splat(float x) { return f32x2{x, x}; }
+
+// The discs of a launch as the collision test reads them: in LDS, two discs per 32-byte record (cx, cx', cy, cy',
+// r2, r2', 0, 0), read back with uniform addresses (a broadcast).  Scalar registers would be the natural home of
+// wave-uniform values, but the rollout kernels have none to spare (they spill ~90 already, into VGPR lanes), and
+// an LDS read takes no VALU issue slot where a v_readlane per operand does.
+constexpr int kObstPairs = MPPI_MAX_OBSTACLES / 2;
+struct ObstR {
+    const float4* rec;   // [2 * kObstPairs] in LDS
+    int n;               // scalar
+};
+struct DiscPair {
+    f32x2 cX, cY, r2;
+};
+// One thread writes the records (constant kernel-argument offsets: a run-time index into the by-value struct would
+// send it through a private copy); the caller's barrier publishes them.
+__device__ __forceinline__ void stage_obst(float4* rec, const ObstK& ob) {
+#pragma unroll
+    for (int p = 0; p < kObstPairs; ++p) {
+        rec[2 * p] = make_float4(ob.cx[2 * p], ob.cx[2 * p + 1], ob.cy[2 * p], ob.cy[2 * p + 1]);
+        rec[2 * p + 1] = make_float4(ob.r2[2 * p], ob.r2[2 * p + 1], 0.f, 0.f);
+    }
+}
+__device__ __forceinline__ DiscPair load_pair(const ObstR& o, int p) {
+    const float4 a = o.rec[2 * p], b = o.rec[2 * p + 1];
+    return DiscPair{f32x2{a.x, a.y}, f32x2{a.z, a.w}, f32x2{b.x, b.y}};
+}
+
+// Does a link touch a disc: two discs (the halves of pX, pY, r2) against the segment from the origin of
+// (pX, pY) — the disc centres relative to the link's base — along the unit direction cs = (cos, sin), length L.
+// The well-conditioned form: project the centre on the direction, clip the parameter to [0, L] with one
+// v_med3_f32 (0 <= L), subtract the foot point and square the offset; nothing cancels at the magnitude of the
+// centre.  Five roundings on the way to d (two in s, one in each offset component, two in the sum of their
+// squares), each at magnitude <= |centre| + L.  Every product-sum is an explicit fma, so the rollout and
+// mppi_debug_obstacle_hits evaluate the same operations whatever the compiler would contract.
+__device__ __forceinline__ void seg_hits(f32x2 pX, f32x2 pY, f32x2 cs, float L, f32x2 r2, bool& ha, bool& hb) {
+    const f32x2 s = __builtin_elementwise_fma(pY, splat(cs.y), pX * splat(cs.x));
+    const f32x2 t = {__builtin_amdgcn_fmed3f(s.x, 0.f, L), __builtin_amdgcn_fmed3f(s.y, 0.f, L)};
+    const f32x2 oX = __builtin_elementwise_fma(-t, splat(cs.x), pX);
+    const f32x2 oY = __builtin_elementwise_fma(-t, splat(cs.y), pY);
+    const f32x2 d = __builtin_elementwise_fma(oY, oY, oX * oX);
+    ha = d.x < r2.x;
+    hb = d.y < r2.y;
+}
+
+// Disc pair p against both links of the arm in the cost's kinematics (fk = (fk_l1, fk_l2), base at the origin):
+// link 1 from the origin along cs1, link 2 from fk_l1 cs1 along cs12.  h[0], h[1]: links 1 and 2 touch disc 2p;
+// h[2], h[3]: disc 2p + 1.
+__device__ __forceinline__ void disc_pair_hits(const ObstR& o, int p, f32x2 cs1, f32x2 cs12, f32x2 fk, bool (&h)[4]) {
+    const DiscPair d = load_pair(o, p);
+    seg_hits(d.cX, d.cY, cs1, fk.x, d.r2, h[0], h[2]);
+    const f32x2 qX = __builtin_elementwise_fma(splat(-fk.x), splat(cs1.x), d.cX);
+    const f32x2 qY = __builtin_elementwise_fma(splat(-fk.x), splat(cs1.y), d.cY);
+    seg_hits(qX, qY, cs12, fk.y, d.r2, h[1], h[3]);
+}
+
+// Does the state (cs1, cs12) collide: the OR over the discs.  NP = 0: a scalar-branched loop over the pairs in
+// use (o.n is wave-uniform); NP > 0: exactly NP pairs, no branch (unused entries are never touched: r2 = -1).
+template <int NP>
+__device__ __forceinline__ bool obst_any(const ObstR& o, f32x2 cs1, f32x2 cs12, f32x2 fk) {
+    bool any = false;
+#pragma unroll
+    for (int p = 0; p < (NP ? NP : kObstPairs); ++p) {
+        if (NP == 0 && 2 * p >= o.n) break;
+        bool h[4];
+        disc_pair_hits(o, p, cs1, cs12, fk, h);
+        any |= (h[0] | h[1]) | (h[2] | h[3]);
+    }
+    return any;
+}
+
+// The same test as a mask (mppi_debug_obstacle_hits): bit 2j link 1 touches disc j, bit 2j + 1 link 2 does.
+__device__ __forceinline__ unsigned obst_mask(const ObstR& o, f32x2 cs1, f32x2 cs12, f32x2 fk) {
+    unsigned m = 0;
+#pragma unroll
+    for (int p = 0; p < kObstPairs; ++p) {
+        if (2 * p >= o.n) break;
+        bool h[4];
+        disc_pair_hits(o, p, cs1, cs12, fk, h);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) m |= (h[b] ? 1u : 0u) << (4 * p + b);
+    }
+    return m;
+}
 
 // (cos, sin) of an angle given in revolutions
 __device__ __forceinline__ f32x2 cossin_rev(float a) { return f32x2{__builtin_amdgcn_cosf(a), __builtin_amdgcn_sinf(a)}; }
@@ -316,13 +414,19 @@ constexpr int kPF = 4;  // noise rows in flight per lane
 // mppi_device.h, which both rollout kernels end with).
 // CLAMP: the sampled controls are clipped to the torque limits (clamp_mode != 0); the CLAMP = false
 // instantiations carry no trace of it.
-template <int LPS, int NT, bool POLL, bool CLAMP>
+// OBST: every step's new state, and the final state once more, is tested against the discs of ob; the count of
+// colliding states times ob.w joins S after the terminal cost.  Every lane of a sample tests every disc, so S
+// does not depend on LPS.  Instantiated with CLAMP only: without torque limits the limits are -+inf, which the
+// median passes v through untouched.
+template <int LPS, int NT, bool POLL, bool CLAMP, bool OBST>
 __global__ __launch_bounds__(NT) void rollout_kernel(
     const KConst c, const StepStatic ss, const DevStep* __restrict__ st, const float2* __restrict__ noise,
     double* __restrict__ S_out, double* __restrict__ slab, double* __restrict__ gslab,
     unsigned* __restrict__ counters, double* __restrict__ partial_out, double* __restrict__ w_eps_out,
     DevStep* __restrict__ nxt, unsigned flags, const XDesc xd, unsigned* __restrict__ epoch, unsigned* __restrict__ tmo,
-    float* __restrict__ upd, const HostOut ho, unsigned long long* __restrict__ dbg, const ClampK cl) {
+    float* __restrict__ upd, const HostOut ho, unsigned long long* __restrict__ dbg, const ClampK cl,
+    const ObstK ob) {
+    static_assert(CLAMP || !OBST, "the OBST kernels are built with CLAMP only");
     __shared__ float4 s_win[kSlots];
     __shared__ float4 s_ua[kMaxT + kPF];   // per-step constants (u_t, a_t); rows >= T repeat row T - 1
     __shared__ double s_redd[NT / 64];
@@ -364,6 +468,14 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     arm_init(x, ss.x0);
     DynK dk = make_dynk(c, sr.cx, sr.cy);
     if constexpr (CLAMP) dynk_limits(dk, cl);
+    ObstR od{};
+    if constexpr (OBST) {
+        __shared__ float4 s_obst[2 * kObstPairs];
+        if (tid == 0) stage_obst(s_obst, ob);   // published by the barrier below
+        od = ObstR{s_obst, __builtin_amdgcn_readfirstlane(ob.n)};
+    }
+    int hits = 0;          // colliding states of this sample so far (OBST)
+    bool hit_last = false; // ... the newest state among them
     // the per-step constants go to LDS: the ring reads them there, so no scalar
     // load shares lgkmcnt with the deferred row lookup below
     for (int i = tid; i < T + kPF; i += NT) s_ua[i] = st->ua[i < T ? i : T - 1];
@@ -406,9 +518,11 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     // exists — 0 no, 1 yes, 2 test t > 0 at run time.  LPS = 1 peels the first
     // step so the unrolled loop body is one basic block (-2.9% at K = 65536);
     // the LPS > 1 kernels keep the test (+5% when peeled at K = 4096).
-    auto dstep = [&](int t, auto slot_c, auto h_c) {
+    // NP (OBST): the disc pairs tested without a branch, or 0 for a scalar branch per pair in use.
+    auto dstep = [&](int t, auto slot_c, auto h_c, auto np_c) {
         constexpr int slot = decltype(slot_c)::value;
         constexpr int H = decltype(h_c)::value;
+        constexpr int NP = decltype(np_c)::value;
         const bool h = H == 2 ? t > 0 : H == 1;
         // The ring slot is fully consumed before its refill is issued: if the old
         // value outlived the new load, the two would need different registers and
@@ -441,6 +555,11 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
                 S4 = f32x2{0.f, 0.f};
             }
         }
+        if constexpr (OBST) {
+            // on the (cos, sin) pairs the step just produced, the ones arm_fk reads below: no transcendental
+            hit_last = obst_any<NP>(od, x.cs1, x.cs12, dk.fk);
+            hits += hit_last ? 1 : 0;
+        }
         pp = arm_fk(x, dk);   // control.py:178-179
         pd = x.dq;
         const f32x2 d = pp - dk.ctr;
@@ -454,41 +573,53 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     using H1 = std::integral_constant<int, 1>;
     using H2 = std::integral_constant<int, 2>;
     static_assert(kPF == 4, "unrolled for a 4-deep ring");
+    // One lane per sample: the unrolled body must stay one basic block (above) and has no registers to spare.
+    // A branch per disc pair inside it, a branch per disc, a rolled loop over the pairs, and a copy of this loop
+    // per pair count each cost 23 to 80 spilled VGPRs (scratch); all four pairs without a branch cost three
+    // registers.  So LPS = 1 tests every pair, the unused ones included (r2 = -1: never touched), and the kernels
+    // with lanes to share branch on the count.
+    using NP = std::integral_constant<int, (OBST && LPS == 1) ? kObstPairs : 0>;
     int t = 0;
     STAMP(12, NOW());
     if constexpr (LPS == 1) {
-        dstep(0, I0{}, H0{});
+        dstep(0, I0{}, H0{}, NP{});
         for (t = 1; t + kPF <= T; t += kPF) {   // slots 1, 2, 3, 0
-            dstep(t, I1{}, H1{});
-            dstep(t + 1, I2{}, H1{});
-            dstep(t + 2, I3{}, H1{});
-            dstep(t + 3, I0{}, H1{});
+            dstep(t, I1{}, H1{}, NP{});
+            dstep(t + 1, I2{}, H1{}, NP{});
+            dstep(t + 2, I3{}, H1{}, NP{});
+            dstep(t + 3, I0{}, H1{}, NP{});
 #ifdef MPPI_STAMPS
             if (t == 1) STAMP(13, NOW());
             if (t + kPF == T / 2 + 1) STAMP(14, NOW());
 #endif
         }
-        if (t < T) dstep(t, I1{}, H1{});          // remainder: t % kPF == 1, 2, 3 in order
-        if (t + 1 < T) dstep(t + 1, I2{}, H1{});
-        if (t + 2 < T) dstep(t + 2, I3{}, H1{});
+        if (t < T) dstep(t, I1{}, H1{}, NP{});          // remainder: t % kPF == 1, 2, 3 in order
+        if (t + 1 < T) dstep(t + 1, I2{}, H1{}, NP{});
+        if (t + 2 < T) dstep(t + 2, I3{}, H1{}, NP{});
     } else {
         for (; t + kPF <= T; t += kPF) {
-            dstep(t, I0{}, H2{});
-            dstep(t + 1, I1{}, H2{});
-            dstep(t + 2, I2{}, H2{});
-            dstep(t + 3, I3{}, H2{});
+            dstep(t, I0{}, H2{}, NP{});
+            dstep(t + 1, I1{}, H2{}, NP{});
+            dstep(t + 2, I2{}, H2{}, NP{});
+            dstep(t + 3, I3{}, H2{}, NP{});
 #ifdef MPPI_STAMPS
             if (t == 0) STAMP(13, NOW());
             if (t + kPF == T / 2) STAMP(14, NOW());
 #endif
         }
-        if (t < T) dstep(t, I0{}, H2{});          // remainder: t % kPF == 0, 1, 2 in order
-        if (t + 1 < T) dstep(t + 1, I1{}, H2{});
-        if (t + 2 < T) dstep(t + 2, I2{}, H2{});
+        if (t < T) dstep(t, I0{}, H2{}, NP{});          // remainder: t % kPF == 0, 1, 2 in order
+        if (t + 1 < T) dstep(t + 1, I1{}, H2{}, NP{});
+        if (t + 2 < T) dstep(t + 2, I2{}, H2{}, NP{});
     }
     add_pending();                       // step T - 1
     S += (double)(S4.x + S4.y);
     S += (double)cost_pk(ee, ef, f32x2{arg_f(c.tw[0]), arg_f(c.tw[1])}, f32x2{arg_f(c.tw[2]), arg_f(c.tw[3])});  // terminal cost, control.py:109
+    if constexpr (OBST) {
+        // the final state once more (the terminal term), then the penalty in one fp64 multiply and add: the
+        // count is exact, so no order of summation can change it
+        hits += hit_last ? 1 : 0;
+        S += ob.w * (double)hits;
+    }
 
     STAMP(1, NOW());
     const bool owner = valid && sr.sub == 0;
@@ -713,6 +844,37 @@ __global__ __launch_bounds__(kThreads) void nearest_debug_kernel(const KConst c,
     }
 }
 
+// Tests (mppi_debug_obstacle_hits): the collision test of every sample and step as the OBST rollout evaluates
+// it — the same dynamics and the same disc_pair_hits on the same (cos, sin) pairs — as a mask per (sample,
+// step), with the four direction values it was evaluated on: mask[k][t], dir[k][t] = (c1, s1, c12, s12).
+__global__ __launch_bounds__(kThreads) void obstacle_debug_kernel(const KConst c, const StepStatic ss,
+                                                                  const DevStep* __restrict__ st,
+                                                                  const float2* __restrict__ noise, int Kn,
+                                                                  unsigned* __restrict__ mask, float4* __restrict__ dir,
+                                                                  const ClampK cl, const ObstK ob) {
+    const int k = blockIdx.x * kThreads + threadIdx.x;
+    const int T = c.T;
+    const float exf = (c.k_offset + k) < c.k_exploit ? 1.f : 0.f;
+    Arm x;
+    arm_init(x, ss.x0);
+    DynK dk = make_dynk(c, 0.f, 0.f);
+    dynk_limits(dk, cl);
+    __shared__ float4 s_obst[2 * kObstPairs];
+    if (threadIdx.x == 0) stage_obst(s_obst, ob);
+    __syncthreads();
+    const ObstR od{s_obst, __builtin_amdgcn_readfirstlane(ob.n)};
+    if (k >= Kn) return;
+    for (int t = 0; t < T; ++t) {
+        const float4 ua = st->ua[t];
+        const float2 e = noise[(size_t)t * c.K_local + k];
+        f32x2 v = __builtin_elementwise_fma(splat(exf), f32x2{ua.x, ua.y}, f32x2{e.x, e.y});
+        v = clamp_v(v, dk);   // as the OBST kernels: always through the median (-+inf without limits)
+        arm_step(x, v, dk);
+        mask[(size_t)k * T + t] = obst_mask(od, x.cs1, x.cs12, dk.fk);
+        dir[(size_t)k * T + t] = make_float4(x.cs1.x, x.cs1.y, x.cs12.x, x.cs12.y);
+    }
+}
+
 // Philox4x32-10 + Box-Muller (mppi_device.h); eps = L z, L = chol(Sigma) (the
 // arguments carry L x kBoxMullerScale, box_muller's constant).
 // Grid (ceil(K_local / kThreads), ceil(T / 2)): blockIdx.y is the step pair, so
@@ -745,6 +907,7 @@ struct mppi_ctx {
     int lps = 1, nt = 256, nblocks = 0;
     KConst kc;
     ClampK ck{};                // torque limits (mode 0: none)
+    ObstK ok{};                 // workspace obstacles of the next launch (n = 0: none), mppi_set_obstacles
     StepStatic stat{};          // x0 + window of the next launch (a kernel argument)
     mppi_host::DevBuf<DevStep> d_step;      // [2] ping-pong nominal
     int cur = 0;
@@ -785,13 +948,20 @@ using mppi_host::launch_check;
 using mppi_host::with_bool;
 using mppi_host::with_value;
 
-// The instantiated rollout kernels: LPS in {1, 2, 4, 8, 16} x NT in {256, 512} x POLL x CLAMP.  Calls
-// f(lps, nt, poll, clamp), the context's instance as integral constants, in the hand-off form `poll`.
+// The instantiated rollout kernels: LPS in {1, 2, 4, 8, 16} x NT in {256, 512} x POLL x (plain, CLAMP,
+// CLAMP + OBST).  Calls f(lps, nt, poll, clamp, obst), the instance of the context's next launch as integral
+// constants, in the hand-off form `poll`.  With discs set the launch goes through the CLAMP + OBST kernel
+// whether or not there are torque limits (without them ClampK holds -+inf, and clamp_mode 0 clips no nominal).
 template <class F>
 void with_rollout(const mppi_ctx* c, bool poll, F&& f) {
     with_value<1, 2, 4, 8, 16>(c->lps, [&](auto lps) {
         with_value<256, 512>(c->nt, [&](auto nt) {
-            with_bool(poll, [&](auto p) { with_bool(c->ck.mode != 0, [&](auto cl) { f(lps, nt, p, cl); }); });
+            with_bool(poll, [&](auto p) {
+                if (c->ok.n > 0)
+                    f(lps, nt, p, std::true_type{}, std::true_type{});
+                else
+                    with_bool(c->ck.mode != 0, [&](auto cl) { f(lps, nt, p, cl, std::false_type{}); });
+            });
         });
     });
 }
@@ -846,8 +1016,8 @@ int alloc(mppi_ctx* c) {
     int ncu = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
     // of the kernel the context will launch (the CLAMP form holds two more register pairs), always its POLL form
-    with_rollout(c, true, [&](auto lps, auto nt, auto p, auto cl) {
-        const void* f = (const void*)rollout_kernel<lps, nt, p, cl>;
+    with_rollout(c, true, [&](auto lps, auto nt, auto p, auto cl, auto ob) {
+        const void* f = (const void*)rollout_kernel<lps, nt, p, cl, ob>;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, nt, 0) != hipSuccess) per_cu = 0;
     });
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + 2 * c->cfg.T, 0)) return rc;
@@ -944,6 +1114,8 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
         ck.v_lo[d] = (float)ck.u_lo[d];
         ck.v_hi[d] = (float)ck.u_hi[d];
     }
+
+    for (int j = 0; j < MPPI_MAX_OBSTACLES; ++j) c->ok.r2[j] = -1.f;   // no discs
 
     if (int rc = alloc(c.get())) return rc;
     *out = c.release();
@@ -1114,11 +1286,11 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
     const DevStep* cur = c->d_step + c->cur;
     DevStep* nxt = c->d_step + (c->cur ^ 1);
     const float2* nz = reinterpret_cast<const float2*>(noise_dev);
-    with_rollout(c, c->hand.poll, [&](auto lps, auto nt, auto p, auto cl) {
-        hipLaunchKernelGGL((rollout_kernel<lps, nt, p, cl>), dim3(c->nblocks), dim3(nt), 0, c->stream, c->kc, c->stat, cur,
+    with_rollout(c, c->hand.poll, [&](auto lps, auto nt, auto p, auto cl, auto ob) {
+        hipLaunchKernelGGL((rollout_kernel<lps, nt, p, cl, ob>), dim3(c->nblocks), dim3(nt), 0, c->stream, c->kc, c->stat, cur,
                            nz, S_dev, c->hand.d_slab, c->hand.d_gslab, c->hand.d_counter, partial_dev, c->d_weps, nxt,
                            flags, c->ex.xd, c->hand.d_epoch, c->hand.h_tmo.dev, reinterpret_cast<float*>(c->d_upd.h),
-                           ho, c->d_dbg, c->ck);
+                           ho, c->d_dbg, c->ck, c->ok);
     });
     const int rc = launch_check("rollout_kernel");
     if (took_update(c, rc, flags)) c->x_flipped = (flags & MPPI_FLAG_EXCHANGE) != 0;   // undone if the exchange fails
@@ -1404,6 +1576,35 @@ int mppi_debug_nearest(mppi_ctx* c, const float* noise_dev, int K, int* slot_dev
                        c->stat, c->d_step + c->cur, reinterpret_cast<const float2*>(noise_dev), K, slot_dev,
                        reinterpret_cast<float2*>(pos_dev), c->ck);
     return launch_check("nearest_debug_kernel");
+}
+
+int mppi_set_obstacles(mppi_ctx* c, int n, const double* discs, double cost) {
+    if (!c) return fail(MPPI_E_ARG, "null context");
+    if (n < 0 || n > MPPI_MAX_OBSTACLES) return fail(MPPI_E_ARG, "obstacles: n must be in [0, 8]");
+    if (n > 0 && !discs) return fail(MPPI_E_ARG, "obstacles: null discs");
+    if (!(cost >= 0.0) || isinf(cost)) return fail(MPPI_E_ARG, "obstacles: the cost must be finite and >= 0");
+    ObstK k{};
+    for (int j = 0; j < MPPI_MAX_OBSTACLES; ++j) k.r2[j] = -1.f;   // below every squared distance: never touched
+    for (int j = 0; j < n; ++j) {
+        const double cx = discs[3 * j], cy = discs[3 * j + 1], r = discs[3 * j + 2];
+        if (!isfinite((float)cx) || !isfinite((float)cy)) return fail(MPPI_E_ARG, "obstacles: a centre is not finite");
+        if (!(r >= 0.0)) return fail(MPPI_E_ARG, "obstacles: a radius is NaN or negative");
+        k.cx[j] = (float)cx;
+        k.cy[j] = (float)cy;
+        k.r2[j] = (float)(r * r);
+    }
+    k.w = cost;
+    k.n = n;
+    c->ok = k;   // read by the next launch of any kind (a kernel argument, by value): no device call
+    return MPPI_OK;
+}
+
+int mppi_debug_obstacle_hits(mppi_ctx* c, const float* noise_dev, int K, unsigned* mask_dev, float* dir_dev) {
+    if (!c || !noise_dev || !mask_dev || !dir_dev || K < 1 || K > c->cfg.K_local) return fail(MPPI_E_ARG, "bad argument");
+    hipLaunchKernelGGL(obstacle_debug_kernel, dim3((K + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, c->kc,
+                       c->stat, c->d_step + c->cur, reinterpret_cast<const float2*>(noise_dev), K, mask_dev,
+                       reinterpret_cast<float4*>(dir_dev), c->ck, c->ok);
+    return launch_check("obstacle_debug_kernel");
 }
 
 int mppi_debug_dropin_times(const mppi_ctx* c, double* us_out) {

@@ -1,0 +1,207 @@
+"""CPU: workspace obstacles (a collision cost on both links of the 2-link arm).
+
+  * tests/obstacle_ref.py, the NumPy restatement the GPU tests use as their yardstick, is pinned to every
+    obst_step_* / obst_loop_* fixture captured from the reference itself (make_golden_obstacle.py: the reference
+    with only _c and _phi overridden): S to 1e-12 relative, every collision flag equal, the clearance, and the
+    returned controls bit for bit where the weights are one-hot;
+  * the fixtures mean something: 10-90 % of the samples collide, the obstacle moves the argmin;
+  * the segment test's geometry on hand-checked poses;
+  * the drop-in's validation of obstacles / obstacle_cost and its by-value comparison key;
+  * the C ABI: the two new entry points are declared in the header and exported by the library.
+"""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import obstacle_ref as R
+from conftest import GOLDEN, ROOT
+from mppi_robotarm_amd.controller import MPPIControllerForPathTracking
+from mppi_robotarm_amd.engine import RolloutEngine
+from obstacle_ref import OBST_STEPS, load_obst_loop, load_obst_step
+
+HEADER = os.path.join(ROOT, "include", "mppi_rocm.h")
+
+
+def ref_step(g, path, discs=None, w=None):
+    return R.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), path, int(g["prev_idx_after"]),
+                  float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
+                  g["stage_cost_weight"], g["terminal_cost_weight"],
+                  g["obstacles"] if discs is None else discs, float(g["obstacle_cost"]) if w is None else w,
+                  g.get("u_min"), g.get("u_max"), expl=float(g["param_exploration"]),
+                  visualize_optimal_traj=bool(g["visualize_optimal_traj"]))
+
+
+def test_the_fixtures_are_all_here():
+    assert OBST_STEPS == ["a_k128_t20", "b_dense_k256_t24", "c_expl_k128_t20", "d_clamp_k128_t20"]
+    assert os.path.exists(os.path.join(GOLDEN, "obst_loop_k64_t20.npz"))
+    # tests/conftest.py globs step_* and loop_* into the unobstructed parity tests: none of ours may match
+    assert not [f for f in os.listdir(GOLDEN) if "obst" in f and f.startswith(("step_", "loop_"))]
+
+
+@pytest.mark.parametrize("name", OBST_STEPS)
+def test_obstacle_ref_matches_the_reference(name, paths):
+    g = load_obst_step(name)
+    r = ref_step(g, paths[str(g["path"])])
+    assert np.array_equal(r["flag"], g["flag"])
+    np.testing.assert_allclose(r["clear"], g["clearance"], rtol=1e-9, atol=1e-13)
+    assert int(np.argmin(r["S"])) == int(np.argmin(g["S"]))
+    assert float(np.max(np.abs(r["S"] - g["S"]) / np.abs(g["S"]))) < 1e-12
+    assert float(np.max(np.abs(r["S_track"] + float(g["obstacle_cost"]) * r["hits"] - g["S"]) / np.abs(g["S"]))) < 1e-12
+    if name == "a_k128_t20":
+        assert np.count_nonzero(g["w"]) == 1
+    if np.count_nonzero(g["w"]) == 1:
+        # one weight is exactly 1 and the rest exactly 0: the update is a copy of one sample's noise, bit for bit
+        assert np.array_equal(r["w_eps_filt"], g["w_eps_filt"])
+        assert np.array_equal(r["u_seq"], g["u_seq"]) and np.array_equal(r["u0"], g["u0"])
+    else:
+        np.testing.assert_allclose(r["w_eps_filt"], g["w_eps_filt"], rtol=1e-10, atol=1e-10)
+        np.testing.assert_allclose(r["u_seq"], g["u_seq"], rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(r["optimal_traj"], g["optimal_traj"], rtol=1e-10, atol=1e-10)
+
+
+@pytest.mark.parametrize("name", OBST_STEPS)
+def test_the_fixtures_exercise_the_feature(name, paths):
+    g = load_obst_step(name)
+    r = ref_step(g, paths[str(g["path"])])
+    r = {**r, "hit": r["dist"] < g["obstacles"][:, 2][None, None, :, None]}
+    share = float(np.mean(g["flag"].any(1)))
+    assert 0.10 <= share <= 0.90
+    assert r["hit"][..., 0].any() and r["hit"][..., 1].any()                       # both links
+    assert (r["hit"] & r["clipped"]).any() and (r["hit"] & ~r["clipped"]).any()    # a clipped and an unclipped foot
+    assert float(np.mean(g["clearance"].min(1) >= 1e-4)) >= 0.80
+    free = ref_step(g, paths[str(g["path"])], discs=np.zeros((0, 3)), w=0.0)
+    assert float(np.max(np.abs(free["S"] - g["S_free"]) / np.abs(g["S_free"]))) < 1e-12
+    assert np.array_equal(free["S"], free["S_track"]) and not free["flag"].any()
+    if bool(g["one_hot"]):
+        k0, order = int(np.argmin(g["S_free"])), np.argsort(g["S"])
+        assert g["flag"][k0].any() and int(order[0]) != k0                        # the obstacle changes the decision
+        assert g["clearance"][order[:2]].min() >= 1e-4
+        assert (g["S"][order[1]] - g["S"][order[0]]) / abs(g["S"][order[0]]) >= 1e-3
+    else:
+        # w of the order of lambda: a collision moves a weight instead of zeroing it
+        wts = g["w"][g["flag"].any(1)]
+        assert np.count_nonzero(wts > 1e-6) >= 10
+
+
+def test_obstacle_ref_matches_the_reference_closed_loop(paths):
+    g = load_obst_loop("k64_t20")
+    from mppi_robotarm_amd.params import runpy_config
+    kw = runpy_config()
+    T = int(g["T"])
+    u_prev = np.array([[10.0, -2.0]] * T)
+    assert 0.10 <= float(np.mean(g["flag"].any(2))) <= 0.90
+    assert not np.allclose(g["u"], g["u_free"])
+    for i in range(int(g["ticks"])):
+        r = R.step(g["states"][i], u_prev, g["eps"][i].astype(np.float64), paths["xydq_circle"],
+                   int(g["prev_idx"][i]), 0.006, kw["param_lambda"], kw["param_alpha"], kw["sigma"],
+                   kw["stage_cost_weight"], kw["terminal_cost_weight"], g["obstacles"], float(g["obstacle_cost"]))
+        assert np.array_equal(r["flag"], g["flag"][i]), i
+        assert float(np.max(np.abs(r["S"] - g["S"][i]) / np.abs(g["S"][i]))) < 1e-12, i
+        np.testing.assert_allclose(r["u_seq"], g["u_seq"][i], rtol=1e-10, atol=1e-10)
+        u_prev = g["u_seq"][i].copy()
+
+
+def test_segment_geometry():
+    """Hand-checked poses: q1 = 0, q2 = pi / 2 puts link 1 on the x axis from 0 to 1 and link 2 from (1, 0) up
+    to (1, 1)."""
+    discs = np.array([[0.5, 0.05, 0.1],     # beside link 1's interior: foot unclipped, d = 0.05
+                      [-0.3, 0.0, 0.2],     # behind the base: clipped to s = 0, d = 0.3: no touch
+                      [-0.1, 0.0, 0.2],     # behind the base, within reach: clipped, d = 0.1
+                      [1.0, 1.25, 0.3],     # above link 2's tip: clipped to s = L, d = 0.25
+                      [1.2, 0.5, 0.2],      # beside link 2: d = 0.2, not < r: the boundary does not touch
+                      [1.2, 0.5, 0.2000001]])
+    flag, clear, dist, clipped = R.collides(np.array(0.0), np.array(np.pi / 2), discs)
+    np.testing.assert_allclose(dist[:, 0], [0.05, 0.3, 0.1, 1.25, np.hypot(0.2, 0.5), np.hypot(0.2, 0.5)], atol=1e-12)
+    np.testing.assert_allclose(dist[3, 1], 0.25, atol=1e-12)
+    np.testing.assert_allclose(dist[4:, 1], [0.2, 0.2], atol=1e-12)
+    hit = dist < discs[:, 2][:, None]
+    assert hit[:, 0].tolist() == [True, False, True, False, False, False]
+    assert hit[:, 1].tolist() == [False, False, False, True, bool(dist[4, 1] < 0.2), True]
+    assert clipped[:, 0].tolist() == [False, True, True, False, True, True]
+    assert bool(clipped[3, 1]) and not bool(clipped[4, 1])
+    assert R.touch_mask(dist, discs) == sum(1 << (2 * j + l) for j in range(6) for l in range(2) if hit[j, l])
+    assert bool(flag)
+    none = R.collides(np.array(0.0), np.array(np.pi / 2), np.zeros((0, 3)))
+    assert not bool(none[0]) and np.isinf(none[1])
+
+
+def _ctrl(paths, **kw):
+    return MPPIControllerForPathTracking(delta_t=0.006, ref_path=paths["xydq_circle"], horizon_step_T=8,
+                                         number_of_samples_K=16, verbose=False, sigma=np.eye(2) * 20.0, **kw)
+
+
+@pytest.mark.parametrize("bad", [
+    dict(obstacles=[[0.0, 0.0]]), dict(obstacles=[0.0, 0.0, 0.1, 0.2]), dict(obstacles=np.zeros((9, 3))),
+    dict(obstacles=[[0.0, 0.0, -0.1]]), dict(obstacles=[[0.0, 0.0, float("nan")]]),
+    dict(obstacles=[[float("inf"), 0.0, 0.1]]), dict(obstacles=[[0.0, float("nan"), 0.1]]),
+    dict(obstacles=[[0.0, 0.0, 0.1]], obstacle_cost=-1.0), dict(obstacles=[[0.0, 0.0, 0.1]], obstacle_cost=float("nan")),
+    dict(obstacles=[[0.0, 0.0, 0.1]], obstacle_cost=float("inf")), dict(obstacles=[[0.0, 0.0, 0.1], [1.0, 2.0]]),
+    dict(obstacles="discs")])
+def test_validation(paths, bad):
+    with pytest.raises(ValueError):
+        _ctrl(paths, **bad)
+    c = _ctrl(paths)
+    for k, v in bad.items():
+        setattr(c, k, v)
+    state = np.random.get_state()
+    with pytest.raises(ValueError):
+        c.calc_control_input(np.zeros(4))       # before any RNG draw, and before a GPU is needed
+    assert all(np.array_equal(a, b) for a, b in zip(state, np.random.get_state()))
+    assert c.prev_waypoints_idx == 0
+    with pytest.raises(ValueError):
+        RolloutEngine.check_obstacles(bad["obstacles"], bad.get("obstacle_cost", 1.0))
+
+
+def test_obstacles_are_plain_attributes_compared_by_value(paths):
+    c = _ctrl(paths)
+    assert c.obstacles is None and c.obstacle_cost == 1.0e10 and c._obstacle_key() is None
+    c.obstacles = []
+    assert c._obstacle_key() is None
+    d = np.array([[1.0, 0.5, 0.1], [0.2, 0.3, 0.0]])
+    c = _ctrl(paths, obstacles=d, obstacle_cost=5.0)
+    k = c._obstacle_key()
+    assert k == c._obstacle_key()
+    d[0, 2] = 0.2                                # an in-place edit
+    assert c._obstacle_key() != k
+    k = c._obstacle_key()
+    c.obstacles = d.tolist()                     # a rebind to an equal value
+    assert c._obstacle_key() == k
+    c.obstacle_cost = 6.0
+    assert c._obstacle_key() != k
+    a, w = RolloutEngine.check_obstacles([(1, 2, 3)], 7)
+    assert a.dtype == np.float64 and a.shape == (1, 3) and a.flags.c_contiguous and w == 7.0
+    assert RolloutEngine.check_obstacles(None, 0.0)[0].shape == (0, 3)
+    assert RolloutEngine.check_obstacles(np.zeros((8, 3)), 0.0)[0].shape == (8, 3)
+
+
+def test_the_new_parameters_are_keyword_only():
+    """obstacles / obstacle_cost are keyword-only, so the twelve positional arguments stay control.py:21-35's."""
+    import inspect
+    params = inspect.signature(MPPIControllerForPathTracking.__init__).parameters
+    assert params["obstacles"].kind is inspect.Parameter.KEYWORD_ONLY and params["obstacles"].default is None
+    assert params["obstacle_cost"].kind is inspect.Parameter.KEYWORD_ONLY and params["obstacle_cost"].default == 1.0e10
+    positional = [n for n, q in params.items() if q.kind is inspect.Parameter.POSITIONAL_OR_KEYWORD]
+    assert len(positional) == 13 and positional[-1] == "visualze_sampled_trajs"      # self + the reference's twelve
+
+
+def test_the_entry_points_are_declared_and_exported():
+    from mppi_robotarm_amd import _native
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    for name in ("mppi_set_obstacles", "mppi_debug_obstacle_hits"):
+        assert re.search(rf"\bint {name}\s*\(\s*mppi_ctx \*", text), name
+        assert name in _native.EXPORTS
+    m = re.search(r"#define MPPI_MAX_OBSTACLES\s+(\d+)", text)
+    assert m and int(m.group(1)) == _native.MPPI_MAX_OBSTACLES == 8
+    if not os.path.exists(_native.LIB_PATH):
+        from mppi_robotarm_amd.build import build_native
+        build_native()
+    lib = _native.load()
+    nm = subprocess.run(["nm", "-D", "--defined-only", _native.LIB_PATH], capture_output=True, text=True).stdout
+    for name in ("mppi_set_obstacles", "mppi_debug_obstacle_hits"):
+        assert hasattr(lib, name) and getattr(lib, name).argtypes is not None
+        assert re.search(rf"\bT {name}\b", nm), name
+    # no context: an argument error, not a crash
+    assert lib.mppi_set_obstacles(None, 0, None, 0.0) == _native.MPPI_E_ARG
