@@ -138,24 +138,35 @@ def chain_state_cost(q, dq, ref_path, prev_idx, weight, P: ChainParams):
     return c * 10000
 
 
+def chain_model(P: ChainParams = ChainParams()):
+    """The chain for mppi_oracle's horizon loop and update tail (O.Model); the state is (q, dq), each (K, n)."""
+    n = P.n
+    return O.Model(start=lambda x0, K: (np.tile(np.asarray(x0[:n], dtype=np.float64), (K, 1)),
+                                        np.tile(np.asarray(x0[n:], dtype=np.float64), (K, 1))),
+                   step=lambda s, v, dt: chain_forward_dynamics(*s, v, dt, P),
+                   cost=lambda s, ref_path, prev_idx, weight: chain_state_cost(*s, ref_path, prev_idx, weight, P),
+                   dot=lambda a, v: v @ a,
+                   trajectory=lambda x0, controls, dt: chain_rollout_trajectory(x0, controls, dt, P))
+
+
 def chain_rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
-                        expl=0.0, P: ChainParams = ChainParams(), k_offset=0, K_total=None):
-    """The K x T loop (control.py:81-109 with the chain model).  eps (K, T, n); returns S (K,)."""
-    K, T, n = eps.shape
-    K_total = K if K_total is None else K_total
-    gamma = lam * (1.0 - alpha)
-    sig_inv = np.linalg.inv(sigma)
-    exploit = (np.arange(K) + k_offset) < (1.0 - expl) * K_total
-    q = np.tile(np.asarray(x0[:n], dtype=np.float64), (K, 1))
-    dq = np.tile(np.asarray(x0[n:], dtype=np.float64), (K, 1))
-    S = np.zeros(K)
-    for t in range(T):
-        e = eps[:, t, :].astype(np.float64)
-        v = np.where(exploit[:, None], u[t] + e, e)
-        q, dq = chain_forward_dynamics(q, dq, v, dt, P)
-        a = (gamma * u[t]) @ sig_inv
-        S = S + (chain_state_cost(q, dq, ref_path, prev_idx, stage_w, P) + v @ a)
-    return S + chain_state_cost(q, dq, ref_path, prev_idx, term_w, P)
+                        expl=0.0, P: ChainParams = ChainParams(), k_offset=0, K_total=None, *, gamma=None,
+                        lo=None, hi=None):
+    """The K x T loop (control.py:81-109 with the chain model, O.horizon_loop).  eps (K, T, n); returns S (K,).
+    ``lo`` / ``hi``: torque limits, a scalar or per joint (the four rules of O.sampled_controls, per joint)."""
+    return O.horizon_loop(chain_model(P), x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
+                          expl, k_offset, K_total, gamma, lo, hi)[0]
+
+
+def step(x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
+         P: ChainParams = ChainParams(), *, gamma=None, lo=None, hi=None, visualize_optimal_traj=True, sampled=False):
+    """One calc_control_input after its waypoint update, with limits when given; ``prev_idx`` is the updated
+    index.  Returns S joined with O.update_in_place's dict."""
+    u = np.array(u_prev, dtype=np.float64)
+    S = chain_rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl, P,
+                            gamma=gamma, lo=lo, hi=hi)
+    return dict(S=S, **O.update_in_place(chain_model(P), S, u, eps, lam, x0, dt, lo, hi, expl,
+                                         visualize_optimal_traj, sampled))
 
 
 def chain_rollout_trajectory(x0, controls, dt, P: ChainParams = ChainParams()):
@@ -185,8 +196,9 @@ class ChainOracleController:
 
     def __init__(self, delta_t, ref_path, horizon_step_T, number_of_samples_K, param_exploration, param_lambda,
                  param_alpha, sigma, stage_cost_weight, terminal_cost_weight, chain: ChainParams = ChainParams(),
-                 u_init=None, visualize_optimal_traj=True, visualze_sampled_trajs=False):
+                 u_init=None, visualize_optimal_traj=True, visualze_sampled_trajs=False, *, u_min=None, u_max=None):
         self.chain = chain
+        self.u_min, self.u_max = u_min, u_max
         self.dim_u, self.dim_x = chain.n, 2 * chain.n
         self.T, self.K = horizon_step_T, number_of_samples_K
         self.param_exploration, self.param_lambda, self.param_alpha = param_exploration, param_lambda, param_alpha
@@ -211,22 +223,10 @@ class ChainOracleController:
         eps = np.asarray(epsilon, dtype=np.float64)
         S = chain_rollout_costs(x0, u, eps, self.ref_path, self.prev_waypoints_idx, self.delta_t,
                                 self.param_lambda, self.param_alpha, self.Sigma, self.stage_cost_weight,
-                                self.terminal_cost_weight, self.param_exploration, self.chain)
-        w = O.compute_weights(S, self.param_lambda)
-        w_eps_raw = O.weighted_noise(w, eps)
-        w_eps = O.moving_median_filter(w_eps_raw, 10)
-        u_before = u.copy()
-        u += w_eps
-        u_new = u.copy()
-        optimal = np.zeros((self.T, self.dim_x))
-        if self.visualize_optimal_traj:
-            optimal = chain_rollout_trajectory(x0, np.roll(u, 1, axis=0), self.delta_t, self.chain)
-        sampled = np.zeros((self.K, self.T, self.dim_x))
-        if self.visualze_sampled_trajs:
-            kx = (np.arange(self.K) < (1.0 - self.param_exploration) * self.K)[:, None, None]
-            v = np.where(kx, u_before[None] + eps, eps)
-            sampled = chain_rollout_trajectory(x0, np.roll(v, 1, axis=1), self.delta_t, self.chain)
-        self.u_prev[:-1] = u[1:]
-        self.u_prev[-1] = u[-1]
-        self.last = dict(S=S, w=w, w_eps_raw=w_eps_raw, w_eps_filt=w_eps, u_new=u_new, eps=eps)
-        return u[0], u, optimal, sampled
+                                self.terminal_cost_weight, self.param_exploration, self.chain,
+                                lo=self.u_min, hi=self.u_max)
+        r = O.update_in_place(chain_model(self.chain), S, u, eps, self.param_lambda, x0, self.delta_t, self.u_min,
+                              self.u_max, self.param_exploration, self.visualize_optimal_traj,
+                              self.visualze_sampled_trajs)
+        self.last = dict(S=S, eps=eps, **r)
+        return r["u0"], u, r["optimal_traj"], r["sampled_traj"]

@@ -8,7 +8,14 @@ checker.  The HIP product path (``mppi_robotarm_amd``) never imports this file.
 Parity is PINNED: ``tests/test_oracle_golden.py`` checks this restatement
 against the golden fixtures captured from the imported reference
 (``tests/golden/make_golden.py``) — S to ~1e-15 relative, u bit-for-bit in the
-one-hot regime, closed loops tick by tick.
+one-hot regime, closed loops tick by tick.  The same loop and update tail, with
+torque limits (``lo`` / ``hi``: the reference's clamp hook ``_g`` switched on)
+and with workspace obstacles (``discs``: a collision cost inside ``_c`` and
+``_phi``), are pinned by ``tests/test_clamp_cpu.py`` and
+``tests/test_obstacle_cpu.py`` to fixtures captured from the reference with
+only those hooks overridden.  There is ONE horizon loop (``horizon_loop``) and
+ONE update tail (``update_in_place``); the chain (``chain_oracle.py``) runs the
+same two with its own model.
 
 Every function cites the reference line it restates.  Quirks kept on purpose
 (SURVEY §3.3): the returned ``u0`` is the post-shift row, ``u_seq`` aliases
@@ -21,6 +28,7 @@ kinematics in the cost (``self.l1 = self.l2 = 1``) keep separate lengths.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -143,37 +151,176 @@ def state_cost(q1, q2, dq1, dq2, ref_path, prev_idx, weight, p: ArmParams):
     return c * 10000
 
 
-def rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
-                  expl=0.0, p: ArmParams = ArmParams(), k_offset=0, K_total=None, gamma=None):
-    """The K x T hot loop, control.py:81-109.  Returns S (K,) fp64.
+def _limits(lo, hi, n):
+    """(lo, hi) per joint from scalars or n values, a missing side +-inf; None when there are no limits."""
+    if lo is None and hi is None:
+        return None
+    return (np.broadcast_to(np.asarray(-np.inf if lo is None else lo, dtype=np.float64), (n,)),
+            np.broadcast_to(np.asarray(np.inf if hi is None else hi, dtype=np.float64), (n,)))
 
-    ``k_offset`` / ``K_total`` restate the exploration split
-    ``k < (1 - expl) * K`` (control.py:98) for a shard of a larger sample set.
-    ``gamma``: the controller's ``param_gamma`` (fixed at construction,
-    control.py:45, read at :106); default lam (1 - alpha).
-    """
-    K, T, _ = eps.shape
-    K_total = K if K_total is None else K_total
+
+def sampled_controls(u, eps, lo=None, hi=None, expl=0.0, k_offset=0, K_total=None):
+    """v: u + eps for the exploitation samples, eps for the rest (control.py:98-104), for any n; eps (K, T, n)
+    with u (T, n), or one step's eps (K, n) with its row of u.  With limits, the reference's clamp hook ``_g``
+    (control.py:166-172) switched on.  ``_g`` ships with its two ``np.clip`` lines commented out; enabled, it
+    clips its argument IN PLACE, and every argument it is given is a view (``v[k, t-1]``, ``u[t-1]``), so:
+
+      1. rollout (control.py:97-106): ``v = clip(u[t-1] + eps)`` (``clip(eps)`` for an exploration sample);
+         ``_F`` and the control cost ``gamma u^T Sigma^-1 v`` take the clipped ``v``;
+      2. weights and weighted noise (control.py:112-118): unchanged, the UNCLAMPED eps;
+      3. update (control.py:126-134): ``u += w_eps`` is not clipped by itself; the optimal-trajectory loop calls
+         ``_g(u[t-1])`` for every row, which clips the whole updated ``u`` in place, only when
+         ``visualize_optimal_traj``;
+      4. sampled trajectories (control.py:139-145): re-rolled from the clipped ``v``.
+
+    ``k_offset`` / ``K_total`` restate the exploration split ``k < (1 - expl) * K`` (control.py:98) for a shard
+    of a larger sample set."""
+    exploit = _exploit(eps.shape[0], expl, k_offset, K_total)
+    return _controls(u, eps, exploit.reshape((-1,) + (1,) * (eps.ndim - 1)), _limits(lo, hi, eps.shape[-1]))
+
+
+def _exploit(K, expl, k_offset, K_total):
+    return (np.arange(K) + k_offset) < (1.0 - expl) * (K if K_total is None else K_total)   # control.py:98
+
+
+def _controls(u, eps, exploit, lim):
+    e = eps.astype(np.float64)
+    v = np.where(exploit, u + e, e)
+    return v if lim is None else np.clip(v, *lim)
+
+
+# What the one horizon loop and the one update tail need of a model (the chain's is chain_oracle.chain_model):
+# start(x0, K) -> state, step(state, v, dt) -> state, cost(state, ref_path, prev_idx, weight) -> (K,),
+# dot(a, v) -> (K,) the control cost a . v in the model's own expression (its bits are pinned), and
+# trajectory(x0, controls, dt) -> states.
+Model = namedtuple("Model", "start step cost dot trajectory")
+
+
+def arm_model(p: ArmParams = ArmParams()):
+    return Model(start=lambda x0, K: tuple(np.full(K, float(x0[i])) for i in range(4)),
+                 step=lambda s, v, dt: forward_dynamics(*s, v[:, 0], v[:, 1], dt, p),
+                 cost=lambda s, ref_path, prev_idx, weight: state_cost(*s, ref_path, prev_idx, weight, p),
+                 dot=lambda a, v: a[0] * v[:, 0] + a[1] * v[:, 1],
+                 trajectory=lambda x0, controls, dt: rollout_trajectory(x0, controls, dt, p))
+
+
+def horizon_loop(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
+                 k_offset=0, K_total=None, gamma=None, lo=None, hi=None, penalty=None):
+    """The K x T hot loop, control.py:81-109, for either model.  Returns (S (K,) fp64, S_track).
+
+    ``penalty(t, state)``, when given, is added to the state cost of step t inside ``_c`` and, its last value,
+    to ``_phi``; S_track is then the same loop without it (None otherwise, and no work is done for it).
+    ``gamma``: the controller's ``param_gamma`` (fixed at construction, control.py:45, read at :106); default
+    lam (1 - alpha)."""
+    K, T, n = eps.shape
     if gamma is None:
         gamma = lam * (1.0 - alpha)                   # control.py:45
     sig_inv = np.linalg.inv(sigma)                    # control.py:106 (raises on singular)
-    kg = np.arange(K) + k_offset
-    exploit = kg < (1.0 - expl) * K_total             # control.py:98
-    S = np.zeros(K)
-    q1 = np.full(K, float(x0[0]))
-    q2 = np.full(K, float(x0[1]))
-    dq1 = np.full(K, float(x0[2]))
-    dq2 = np.full(K, float(x0[3]))
-    for t in range(1, T + 1):
-        e = eps[:, t - 1, :].astype(np.float64)
-        v1 = np.where(exploit, u[t - 1, 0] + e[:, 0], e[:, 0])   # control.py:99-101
-        v2 = np.where(exploit, u[t - 1, 1] + e[:, 1], e[:, 1])
-        q1, q2, dq1, dq2 = forward_dynamics(q1, q2, dq1, dq2, v1, v2, dt, p)
-        c = state_cost(q1, q2, dq1, dq2, ref_path, prev_idx, stage_w, p)
-        a = (gamma * u[t - 1].T) @ sig_inv            # ((γ uᵀ) Σ⁻¹) v, left-to-right
-        S = S + (c + (a[0] * v1 + a[1] * v2))
-    S = S + state_cost(q1, q2, dq1, dq2, ref_path, prev_idx, term_w, p)   # control.py:109
-    return S
+    exploit, lim = _exploit(K, expl, k_offset, K_total)[:, None], _limits(lo, hi, n)
+    S, S_track, pen = np.zeros(K), None if penalty is None else np.zeros(K), 0.0
+    state = model.start(x0, K)
+    for t in range(T):
+        v = _controls(u[t], eps[:, t], exploit, lim)      # control.py:99-104, one step of sampled_controls
+        state = model.step(state, v, dt)
+        c = model.cost(state, ref_path, prev_idx, stage_w)
+        ctrl = model.dot((gamma * u[t].T) @ sig_inv, v)   # ((γ uᵀ) Σ⁻¹) v, left-to-right
+        if penalty is not None:
+            pen = penalty(t, state)
+            S_track = S_track + (c + ctrl)
+            c = c + pen
+        S = S + (c + ctrl)
+    phi = model.cost(state, ref_path, prev_idx, term_w)   # control.py:109
+    if penalty is not None:
+        S_track = S_track + phi
+        phi = phi + pen
+    return S + phi, S_track
+
+
+def rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
+                  expl=0.0, p: ArmParams = ArmParams(), k_offset=0, K_total=None, gamma=None, *,
+                  lo=None, hi=None, discs=None, obstacle_cost=0.0, details=False):
+    """S (K,) fp64 of the arm's K x T loop (horizon_loop), optionally with torque limits ``lo`` / ``hi`` (a
+    scalar or per joint; sampled_controls has the clamp's rules) and the collision cost on ``discs``.
+
+    The collision cost is the reference with ONLY ``_c`` and ``_phi`` (control.py:174-198) overridden to return
+    ``... + obstacle_cost * collides(x)``, the penalty added after the x 10000: every step of the horizon whose
+    new state collides adds it to its sample's cost and the final state adds it once more, so
+    ``S = S_track + obstacle_cost * hits`` with ``hits`` in ``[0, T + 1]``.
+
+    ``details=True`` returns a dict instead: S, S_track (K,) (the same loop without the penalty), flag (K, T)
+    bool per step's new state, clear (K, T) clearance, hits (K,) = flag.sum(1) + flag[:, -1], dist (K, T, n, 2),
+    clipped (K, T, n, 2), ee (K, T, 2) end effector, q (K, T, 2) joint angles, dq (K, T, 2) joint rates.
+    Without discs and without details the loop does no collision or bookkeeping work."""
+    rec, penalty = None, None
+    if discs is not None or details:
+        K, T, _ = eps.shape
+        discs = np.asarray(np.zeros((0, 3)) if discs is None else discs, dtype=np.float64).reshape(-1, 3)
+        n = discs.shape[0]
+        rec = dict(flag=np.zeros((K, T), dtype=bool), clear=np.zeros((K, T)), dist=np.zeros((K, T, n, 2)),
+                   clipped=np.zeros((K, T, n, 2), dtype=bool), ee=np.zeros((K, T, 2)), q=np.zeros((K, T, 2)),
+                   dq=np.zeros((K, T, 2)))
+
+        def penalty(t, state):
+            q1, q2, dq1, dq2 = state
+            rec["flag"][:, t], rec["clear"][:, t], rec["dist"][:, t], rec["clipped"][:, t] = collides(q1, q2, discs, p)
+            rec["ee"][:, t, 0] = p.fk_l1 * np.cos(q1) + p.fk_l2 * np.cos(q1 + q2)
+            rec["ee"][:, t, 1] = p.fk_l1 * np.sin(q1) + p.fk_l2 * np.sin(q1 + q2)
+            rec["q"][:, t, 0], rec["q"][:, t, 1] = q1, q2
+            rec["dq"][:, t, 0], rec["dq"][:, t, 1] = dq1, dq2
+            return obstacle_cost * rec["flag"][:, t]
+
+    S, S_track = horizon_loop(arm_model(p), x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
+                              expl, k_offset, K_total, gamma, lo, hi, penalty)
+    if not details:
+        return S
+    return dict(S=S, S_track=S_track, hits=rec["flag"].sum(1) + rec["flag"][:, -1], **rec)
+
+
+def segment_test(c1, s1, c12, s12, discs, fk1=1.0, fk2=1.0):
+    """Both links against every disc ``(cx, cy, r)`` from the direction values (any common shape).  A link is a
+    zero-thickness segment in the cost's kinematics (``fk_l1``, ``fk_l2``, base at the origin, as ``_c``
+    computes x and y): link 1 from (0, 0) to e = fk_l1 (cos q1, sin q1), link 2 from e to
+    e + fk_l2 (cos(q1 + q2), sin(q1 + q2)).  Returns (dist (..., n, 2) fp64, the distance from disc j's centre
+    to link 1 / link 2, the projection parameter clipped to the segment, and clipped (..., n, 2), whether it was
+    clipped to an end of the segment)."""
+    d = np.asarray(discs, dtype=np.float64).reshape(-1, 3)
+    c1, s1, c12, s12 = (np.asarray(a, dtype=np.float64)[..., None] for a in (c1, s1, c12, s12))
+    cx, cy = d[:, 0], d[:, 1]
+
+    def seg(px, py, ux, uy, L):
+        s = px * ux + py * uy
+        t = np.clip(s, 0.0, L)
+        return np.hypot(px - t * ux, py - t * uy), t != s
+
+    d1, k1 = seg(cx, cy, c1, s1, fk1)
+    d2, k2 = seg(cx - fk1 * c1, cy - fk1 * s1, c12, s12, fk2)
+    return np.stack([d1, d2], -1), np.stack([k1, k2], -1)
+
+
+def touch_mask(dist, discs):
+    """The masks of mppi_debug_obstacle_hits from segment_test's distances: bit 2j link 1 touches disc j,
+    bit 2j + 1 link 2 does (uint32, dist's shape without its last two axes)."""
+    r = np.asarray(discs, dtype=np.float64).reshape(-1, 3)[:, 2]
+    hit = dist < r[:, None]
+    n = hit.shape[-2]
+    bits = (np.uint32(1) << np.arange(2 * n, dtype=np.uint32)).reshape(n, 2)
+    return np.sum(np.where(hit, bits, np.uint32(0)), axis=(-1, -2), dtype=np.uint32)
+
+
+def clearance(dist, discs):
+    """|d - r| of the nearest boundary over discs and links (inf without discs)."""
+    r = np.asarray(discs, dtype=np.float64).reshape(-1, 3)[:, 2]
+    gap = np.abs(dist - r[:, None])
+    return gap.reshape(gap.shape[:-2] + (-1,)).min(-1) if gap.shape[-2] else np.full(gap.shape[:-2], np.inf)
+
+
+def collides(q1, q2, discs, p: ArmParams = ArmParams()):
+    """(flag, clearance, dist, clipped) of the states (q1, q2) against the discs: a state collides when either
+    link touches a disc, its distance to the centre (segment_test) ``< r``."""
+    dist, clipped = segment_test(np.cos(q1), np.sin(q1), np.cos(q1 + q2), np.sin(q1 + q2), discs, p.fk_l1, p.fk_l2)
+    r = np.asarray(discs, dtype=np.float64).reshape(-1, 3)[:, 2]
+    flag = np.any(dist < r[:, None], axis=(-1, -2))
+    return flag, clearance(dist, discs), dist, clipped
 
 
 def compute_weights(S, lam):
@@ -243,6 +390,53 @@ def rollout_trajectory(x0, controls, dt, p: ArmParams = ArmParams()):
     return out
 
 
+def update_in_place(model, S, u, eps, lam, x0, dt, lo=None, hi=None, expl=0.0, visualize_optimal_traj=True,
+                    sampled=False):
+    """The update tail, control.py:112-152, from the costs S: weights, weighted noise, median filter,
+    ``u += w_eps``, the trajectories, the shift.  ``u`` (T, n) is updated IN PLACE, as the reference updates its
+    ``u_prev``.  With limits the updated nominal is clipped only when ``visualize_optimal_traj`` (``_g`` in
+    place, rule 3 of sampled_controls).  Returns w, w_eps_raw, w_eps_filt, u_new (the update before any clip),
+    u_seq (``u`` itself, shifted: what the reference returns and keeps), u0 (its first row, the post-shift one),
+    optimal_traj and sampled_traj (zeros when off)."""
+    K, T, n = eps.shape
+    w = compute_weights(S, lam)
+    w_eps_raw = weighted_noise(w, eps)
+    w_eps_filt = moving_median_filter(w_eps_raw, 10)
+    v = sampled_controls(u, eps, lo, hi, expl) if sampled else None   # control.py:139-145: from the pre-update u
+    u += w_eps_filt                                                  # control.py:126
+    u_new = u.copy()
+    optimal_traj = np.zeros((T, 2 * n))
+    if visualize_optimal_traj:                                       # control.py:129-134
+        if _limits(lo, hi, n) is not None:
+            np.clip(u, *_limits(lo, hi, n), out=u)                   # _g(u[t-1]) over every row, in place
+        optimal_traj = model.trajectory(x0, np.roll(u, 1, axis=0), dt)
+    sampled_traj = np.zeros((K, T, 2 * n))
+    if sampled:
+        sampled_traj = model.trajectory(x0, np.roll(v, 1, axis=1), dt)
+    u[:-1] = u[1:]                                                   # control.py:148-149 (the last row stays)
+    return dict(w=w, w_eps_raw=w_eps_raw, w_eps_filt=w_eps_filt, u_new=u_new, u_seq=u, u0=u[0],
+                optimal_traj=optimal_traj, sampled_traj=sampled_traj)
+
+
+def update(S, u_prev, eps, lam, x0, dt, lo=None, hi=None, visualize_optimal_traj=True, p: ArmParams = ArmParams()):
+    """update_in_place for the arm on a copy of ``u_prev``: the tail from costs S that a test composed itself."""
+    return update_in_place(arm_model(p), S, np.array(u_prev, dtype=np.float64), eps, lam, x0, dt, lo, hi, 0.0,
+                           visualize_optimal_traj)
+
+
+def step(x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
+         p: ArmParams = ArmParams(), gamma=None, *, lo=None, hi=None, discs=None, obstacle_cost=0.0,
+         visualize_optimal_traj=True, sampled=False):
+    """One calc_control_input after its waypoint update (control.py:81-152), with limits and discs when given;
+    ``prev_idx`` is the updated index.  rollout_costs(details=True)'s dict joined with update_in_place's."""
+    u = np.array(u_prev, dtype=np.float64)
+    out = rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl, p, gamma=gamma,
+                        lo=lo, hi=hi, discs=discs, obstacle_cost=obstacle_cost, details=True)
+    out.update(update_in_place(arm_model(p), out["S"], u, eps, lam, x0, dt, lo, hi, expl, visualize_optimal_traj,
+                               sampled))
+    return out
+
+
 class OracleController:
     """Stateful restatement of ``MPPIControllerForPathTracking`` (control.py:20-152)."""
 
@@ -252,7 +446,7 @@ class OracleController:
                  stage_cost_weight=np.array([10.0, 10.0, 10.0, 10.0]),
                  terminal_cost_weight=np.array([10.0, 10.0, 10.0, 10.0]),
                  visualize_optimal_traj=True, visualze_sampled_trajs=False,
-                 arm: ArmParams = ArmParams()):
+                 arm: ArmParams = ArmParams(), *, u_min=None, u_max=None, obstacles=None, obstacle_cost=1.0e10):
         self.dim_x, self.dim_u = 4, 2
         self.T, self.K = horizon_step_T, number_of_samples_K
         self.param_exploration = param_exploration
@@ -267,6 +461,7 @@ class OracleController:
         self.delta_t = delta_t
         self.ref_path = ref_path
         self.arm = arm
+        self.u_min, self.u_max, self.obstacles, self.obstacle_cost = u_min, u_max, obstacles, obstacle_cost
         self.u_prev = np.array([[10.0, -2.0] for _ in range(self.T)])
         self.prev_waypoints_idx = 0
         self.last = {}
@@ -289,22 +484,10 @@ class OracleController:
         S = rollout_costs(x0, u, eps, self.ref_path, self.prev_waypoints_idx, self.delta_t,
                           self.param_lambda, self.param_alpha, self.Sigma,
                           self.stage_cost_weight, self.terminal_cost_weight,
-                          self.param_exploration, self.arm, gamma=self.param_gamma)
-        w = compute_weights(S, self.param_lambda)
-        w_eps_raw = weighted_noise(w, eps)
-        w_eps = moving_median_filter(w_eps_raw, 10)
-        u_before = u.copy()
-        u += w_eps                                                       # control.py:126
-        u_new = u.copy()
-        optimal_traj = np.zeros((self.T, self.dim_x))
-        if self.visualize_optimal_traj:                                  # control.py:129-134
-            optimal_traj = rollout_trajectory(x0, np.roll(u, 1, axis=0), self.delta_t, self.arm)
-        sampled = np.zeros((self.K, self.T, self.dim_x))
-        if self.visualze_sampled_trajs:                                  # control.py:137-145
-            K_exp = (np.arange(self.K) < (1.0 - self.param_exploration) * self.K)[:, None, None]
-            v = np.where(K_exp, u_before[None] + eps, eps)                # pre-update u
-            sampled = rollout_trajectory(x0, np.roll(v, 1, axis=1), self.delta_t, self.arm)
-        self.u_prev[:-1] = u[1:]                                         # control.py:148-149
-        self.u_prev[-1] = u[-1]
-        self.last = dict(S=S, w=w, w_eps_raw=w_eps_raw, w_eps_filt=w_eps, u_new=u_new, eps=eps)
-        return u[0], u, optimal_traj, sampled
+                          self.param_exploration, self.arm, gamma=self.param_gamma, lo=self.u_min, hi=self.u_max,
+                          discs=self.obstacles, obstacle_cost=self.obstacle_cost)
+        r = update_in_place(arm_model(self.arm), S, u, eps, self.param_lambda, x0, self.delta_t, self.u_min,
+                            self.u_max, self.param_exploration, self.visualize_optimal_traj,
+                            self.visualze_sampled_trajs)
+        self.last = dict(S=S, eps=eps, **r)
+        return r["u0"], u, r["optimal_traj"], r["sampled_traj"]

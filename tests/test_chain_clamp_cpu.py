@@ -1,7 +1,7 @@
 """CPU: torque limits of the n-link chain (mppi_chain_config.clamp_mode / u_min / u_max).
 
-  * tests/chain_clamp_ref.py, the NumPy restatement the GPU tests use as their yardstick, reproduces at n = 2
-    (ChainParams.from_arm2()) every clamp_step_* fixture captured from the reference itself;
+  * oracle/chain_oracle.py with limits (lo / hi), the NumPy restatement the GPU tests use as their yardstick,
+    reproduces at n = 2 (ChainParams.from_arm2()) every clamp_step_* fixture captured from the reference itself;
   * the C ABI: the three new fields' layout against the header (a gcc probe, as test_abi.py), the fields before
     them where they were, mppi_chain_config_init leaves the clamp off, mppi_chain_ctx_create rejects bad limits
     before any device call (so these run without a GPU) and names the field in mppi_last_error;
@@ -14,10 +14,9 @@ import subprocess
 import numpy as np
 import pytest
 
-import chain_clamp_ref as CCR
 import chain_oracle as CO
-from clamp_ref import CLAMP_STEPS, load_clamp_step
 from conftest import ROOT
+from helpers import CLAMP_STEPS, load_clamp_step
 from mppi_robotarm_amd.chain import CHAIN7_SIGMA, ChainMPPIController, ChainParams
 
 HEADER = os.path.join(ROOT, "include", "mppi_rocm.h")
@@ -26,11 +25,11 @@ HEADER = os.path.join(ROOT, "include", "mppi_rocm.h")
 @pytest.mark.parametrize("name", CLAMP_STEPS)
 def test_chain_clamp_ref_at_n2_matches_the_reference(name, paths):
     g = load_clamp_step(name)
-    r = CCR.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), paths[str(g["path"])], int(g["prev_idx_after"]),
-                 float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
-                 g["stage_cost_weight"], g["terminal_cost_weight"], g["u_min"], g["u_max"],
-                 expl=float(g["param_exploration"]), visualize_optimal_traj=bool(g["visualize_optimal_traj"]),
-                 sampled=bool(g["sampled"]), P=CO.ChainParams.from_arm2())
+    r = CO.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), paths[str(g["path"])], int(g["prev_idx_after"]),
+                float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
+                g["stage_cost_weight"], g["terminal_cost_weight"], lo=g["u_min"], hi=g["u_max"],
+                expl=float(g["param_exploration"]), visualize_optimal_traj=bool(g["visualize_optimal_traj"]),
+                sampled=bool(g["sampled"]), P=CO.ChainParams.from_arm2())
     assert int(np.argmin(r["S"])) == int(np.argmin(g["S"]))
     assert float(np.max(np.abs(r["S"] - g["S"]) / np.abs(g["S"]))) < 1e-12
     np.testing.assert_allclose(r["w_eps_filt"], g["w_eps_filt"], rtol=1e-10, atol=1e-10)

@@ -1,7 +1,7 @@
 """CPU: torque limits (the reference's clamp hook _g, control.py:166-172, switched on).
 
-  * tests/clamp_ref.py, the NumPy restatement the GPU tests use as their yardstick, is pinned to every
-    clamp_step_* / clamp_loop_* fixture captured from the reference itself (make_golden_clamp.py);
+  * oracle/mppi_oracle.py with limits (lo / hi), the NumPy restatement the GPU tests use as their yardstick, is
+    pinned to every clamp_step_* / clamp_loop_* fixture captured from the reference itself (make_golden_clamp.py);
   * the drop-in's constructor validation, its _g, and the engine key;
   * the C ABI: mppi_config_init leaves the clamp off, mppi_ctx_create rejects bad limits before any device
     call (so these run without a GPU) and names the field in mppi_last_error.
@@ -12,18 +12,18 @@ import os
 import numpy as np
 import pytest
 
-import clamp_ref as CR
-from clamp_ref import CLAMP_STEPS, load_clamp_loop, load_clamp_step
+import mppi_oracle as O
 from conftest import GOLDEN
+from helpers import CLAMP_STEPS, load_clamp_loop, load_clamp_step
 from mppi_robotarm_amd.controller import MPPIControllerForPathTracking
 
 
 def ref_step(g, path):
-    return CR.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), path, int(g["prev_idx_after"]),
-                   float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
-                   g["stage_cost_weight"], g["terminal_cost_weight"], g["u_min"], g["u_max"],
-                   expl=float(g["param_exploration"]), visualize_optimal_traj=bool(g["visualize_optimal_traj"]),
-                   sampled=bool(g["sampled"]))
+    return O.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), path, int(g["prev_idx_after"]),
+                  float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
+                  g["stage_cost_weight"], g["terminal_cost_weight"], lo=g["u_min"], hi=g["u_max"],
+                  expl=float(g["param_exploration"]), visualize_optimal_traj=bool(g["visualize_optimal_traj"]),
+                  sampled=bool(g["sampled"]))
 
 
 def test_the_fixtures_are_all_here():
@@ -57,9 +57,9 @@ def test_clamp_ref_matches_the_reference_closed_loop(paths):
     T = int(g["T"])
     u_prev = np.array([[10.0, -2.0]] * T)
     for i in range(int(g["ticks"])):
-        r = CR.step(g["states"][i], u_prev, g["eps"][i].astype(np.float64), paths["xydq_circle"],
-                    int(g["prev_idx"][i]), 0.006, kw["param_lambda"], kw["param_alpha"], kw["sigma"],
-                    kw["stage_cost_weight"], kw["terminal_cost_weight"], g["u_min"], g["u_max"])
+        r = O.step(g["states"][i], u_prev, g["eps"][i].astype(np.float64), paths["xydq_circle"],
+                   int(g["prev_idx"][i]), 0.006, kw["param_lambda"], kw["param_alpha"], kw["sigma"],
+                   kw["stage_cost_weight"], kw["terminal_cost_weight"], lo=g["u_min"], hi=g["u_max"])
         assert float(np.max(np.abs(r["S"] - g["S"][i]) / np.abs(g["S"][i]))) < 1e-12, i
         np.testing.assert_allclose(r["u_seq"], g["u_seq"][i], rtol=1e-10, atol=1e-10)
         u_prev = g["u_seq"][i].copy()

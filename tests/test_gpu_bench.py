@@ -10,12 +10,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    torch.cuda.set_device(0)
+from helpers import _gpu  # noqa: E402, F401
 
 
 def _run(monkeypatch, capsys, *argv):

@@ -35,6 +35,7 @@ pytestmark = pytest.mark.gpu
 import chain_oracle as CO  # noqa: E402
 import coracle  # noqa: E402
 from conftest import STEP_FIXTURES, load_step, record  # noqa: E402
+from helpers import _gpu, _urel  # noqa: E402, F401
 from tieflip import device_pick_residual, tie_flip_residual  # noqa: E402
 
 U_TOL = 1e-4
@@ -42,17 +43,6 @@ S_TOL = 5e-5
 TIE_GAP_M = 1e-5   # a tie: the two nearest slots' distances within 10 um of each other (the slots are 60 um apart)
 PICK_GAP_M = 1e-6  # a pick the device makes differently from fp64: the two distances within 1 um (measured <= 0.34 um)
 W, TW = [0.5, 0.5, 5.0, 5.0], [5.0, 5.0, 50.0, 50.0]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    torch.cuda.set_device(0)
-
-
-def _urel(a, b):
-    return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
 
 
 def _c5():

@@ -9,7 +9,7 @@ the device median); n in {2, 3, 7} (n = 3 and 7 have a pad link in the quad form
      host so that the unclamped kernel forms exactly the clipped control; the weights still take the unclamped eps;
   2. limits of +-1e30 against no limits: bit-equal;
   3. the reference's own clamp_step_* fixtures through ChainMPPIController at n = 2;
-  4. n = 7 against tests/chain_clamp_ref.py at the existing n = 7 bounds;
+  4. n = 7 against oracle/chain_oracle.py with limits at the existing n = 7 bounds;
   5. mode 2 through the fused update and the merge;
   6. the trajectory re-rolls and the host trajectory;
   7. the drop-in.
@@ -20,9 +20,9 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-import chain_clamp_ref as CCR  # noqa: E402
 import chain_oracle as CO  # noqa: E402
-from clamp_ref import CLAMP_STEPS, load_clamp_step  # noqa: E402
+import mppi_oracle as O  # noqa: E402
+from helpers import CLAMP_STEPS, _gpu, _inside, _urel, load_clamp_step  # noqa: E402, F401
 
 U_TOL = 1e-4
 S_TOL = 5e-5
@@ -31,21 +31,6 @@ DT, ALPHA, T = 0.006, 0.98, 9
 # (precision, lanes per sample, K): every horizon form of chain_rollout_kernel
 FORMS = [("f32", 1, 1000), ("f32", 4, 300), ("f64", 1, 1000)]
 FORM_IDS = ["f32-lps1", "f32-lps4", "f64"]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    torch.cuda.set_device(0)
-
-
-def _urel(a, b):
-    return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
-
-
-def _inside(u, lo, hi):
-    return bool(np.all((u >= lo) & (u <= hi)))
 
 
 def _chains(n):
@@ -223,7 +208,7 @@ def test_chain_at_n2_reproduces_the_clamped_reference_steps(name, paths):
     c.close()
 
 
-# ---------------------------------------------------------------- 4: n = 7 against chain_clamp_ref
+# ---------------------------------------------------------------- 4: n = 7 against the chain oracle with limits
 
 _REF7 = {}
 
@@ -233,10 +218,10 @@ def _ref7(paths, lam):
     if lam not in _REF7:
         Po, x0, u, lo, hi, eps = _case7(7, 1000)
         win = paths["xydq_circle"][40:70]
-        Sr = CCR.chain_rollout_costs(x0, u, eps, win, 0, DT, lam, ALPHA, _sigma(7), W, TW, lo, hi, P=Po)
+        Sr = CO.chain_rollout_costs(x0, u, eps, win, 0, DT, lam, ALPHA, _sigma(7), W, TW, lo=lo, hi=hi, P=Po)
         wk = np.exp(-(Sr - Sr.min()) / lam)
         wr = np.einsum("k,ktd->td", wk / wk.sum(), eps.astype(np.float64))
-        clipped = CCR.sampled_controls(u, eps, lo, hi) != (u[None] + eps.astype(np.float64))
+        clipped = O.sampled_controls(u, eps, lo, hi) != (u[None] + eps.astype(np.float64))
         assert 0.2 < clipped.mean() < 0.8
         for a in (x0, u, lo, hi, eps, Sr, wr):
             a.setflags(write=False)
@@ -292,9 +277,9 @@ def test_mode_2_clips_the_fused_nominal_and_feeds_the_next_launch(precision, lps
     S2 = torch.empty(K, dtype=torch.float64, device="cuda")
     m2.rollout(noise2, S_out=S2, fused_update=True)
     S2 = S2.cpu().numpy()
-    Sr = CCR.chain_rollout_costs(x0, nom2, eps2, win, 0, DT, lam, ALPHA, _sigma(7), W, TW, lo, hi, P=Po)
+    Sr = CO.chain_rollout_costs(x0, nom2, eps2, win, 0, DT, lam, ALPHA, _sigma(7), W, TW, lo=lo, hi=hi, P=Po)
     rel = np.abs(S2 - Sr) / np.abs(Sr)
-    S_wrong = CCR.chain_rollout_costs(x0, nom1, eps2, win, 0, DT, lam, ALPHA, _sigma(7), W, TW, lo, hi, P=Po)
+    S_wrong = CO.chain_rollout_costs(x0, nom1, eps2, win, 0, DT, lam, ALPHA, _sigma(7), W, TW, lo=lo, hi=hi, P=Po)
     assert float(np.median(np.abs(S_wrong - Sr) / np.abs(Sr))) > 1e-3   # the unclipped nominal would show
     assert float(rel.max()) < 1e-11 if precision == "f64" else float(np.percentile(rel, 99)) < 2e-4
     assert _inside(m2.nominal(), lo, hi)
@@ -329,7 +314,7 @@ def test_clamped_trajectories_match_chain_clamp_ref(paths):
     eng.set_step_inputs(x0, paths["xydq_circle"][40:70], u)
     noise = eng.upload_noise(eps)
     tr = eng.trajectories(base_u=u, noise=noise).double().cpu().numpy()
-    v = CCR.sampled_controls(u, eps, lo, hi, expl=0.25)
+    v = O.sampled_controls(u, eps, lo, hi, expl=0.25)
     np.testing.assert_allclose(tr, CO.chain_rollout_trajectory(x0, np.roll(v, 1, axis=1), DT, Po), rtol=1e-4, atol=1e-4)
     tr0 = eng.trajectories(base_u=un, K=1).double().cpu().numpy()
     ref0 = CO.chain_rollout_trajectory(x0, np.roll(np.clip(un, lo, hi), 1, axis=0), DT, Po)

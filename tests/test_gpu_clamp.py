@@ -1,7 +1,7 @@
 """GPU: torque limits (the reference's clamp hook _g, control.py:166-172, switched on) through every layer.
 
 The fixtures are the reference's own outputs with _g clipping in place (tests/golden/make_golden_clamp.py);
-tests/clamp_ref.py, pinned to them on the CPU (test_clamp_cpu.py), is the yardstick at the other shapes.
+oracle/mppi_oracle.py with limits, pinned to them on the CPU (test_clamp_cpu.py), is the yardstick at the other shapes.
 Tolerances are the suite's (test_gpu_parity.py): u 1e-4, S 5e-5 with the same argmin, trajectories 1e-4.
 """
 import numpy as np
@@ -10,62 +10,18 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-import clamp_ref as CR  # noqa: E402
-from clamp_ref import CLAMP_STEPS, load_clamp_loop, load_clamp_step  # noqa: E402
-from conftest import ctor_kwargs  # noqa: E402
+import mppi_oracle as O  # noqa: E402
+from helpers import (CLAMP_STEPS, RUNPY, X0, _ctrl, _engine, _gpu, _inside, _urel, _window,  # noqa: E402, F401
+                     load_clamp_loop, load_clamp_step)
 
 U_TOL = 1e-4
 S_TOL = 5e-5
 
-RUNPY = dict(param_exploration=0.0, param_lambda=100.0, param_alpha=0.98, sigma=np.eye(2) * 20.0,
-             stage_cost_weight=np.array([0.5, 0.5, 5.0, 5.0]),
-             terminal_cost_weight=np.array([5.0, 5.0, 50.0, 50.0]))
-X0 = np.array([1.152198236517471885e00, -1.266101672070702344e00, 0.0, 0.0])
 LO, HI = np.array([6.0, -5.0]), np.array([12.0, 1.0])
 LPS = (1, 2, 4, 8, 16)
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    torch.cuda.set_device(0)
-
-
-def _urel(a, b):
-    return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
-
-
-def _inside(u, lo, hi):
-    return bool(np.all((u >= lo) & (u <= hi)))
-
-
-def _engine(K, T, lps=0, K_total=None, k_offset=0, u_min=None, u_max=None, clamp_nominal=True, **over):
-    from mppi_robotarm_amd.engine import RolloutEngine
-    from mppi_robotarm_amd.params import ArmParams
-    kw = dict(RUNPY)
-    kw.update(over)
-    return RolloutEngine(K, T, 0.006, kw["param_lambda"], kw["param_alpha"], kw["sigma"],
-                         kw["stage_cost_weight"], kw["terminal_cost_weight"], kw["param_exploration"],
-                         ArmParams(), K_total=K_total, k_offset=k_offset, device=0, lanes_per_sample=lps,
-                         u_min=u_min, u_max=u_max, clamp_nominal=clamp_nominal)
-
-
-def _window(paths, prev=0):
-    return paths["xydq_circle"][prev:prev + 30]
-
-
 # ---------------------------------------------------------------- 1, 2: the reference's own outputs
-
-def _ctrl(g, paths, **kw):
-    from mppi_robotarm_amd.controller import MPPIControllerForPathTracking
-    c = MPPIControllerForPathTracking(ref_path=paths[str(g["path"])], verbose=False,
-                                      visualize_optimal_traj=bool(g["visualize_optimal_traj"]),
-                                      u_min=g["u_min"], u_max=g["u_max"], **ctor_kwargs(g), **kw)
-    c.prev_waypoints_idx = int(g["prev_idx"])
-    c.u_prev = g["u_prev"].copy()
-    return c
-
 
 @pytest.mark.parametrize("how", ["general", "host_update", "device_noise"])
 @pytest.mark.parametrize("name", CLAMP_STEPS)
@@ -132,7 +88,7 @@ def test_clamped_closed_loop_ticks(paths):
     c.close()
 
 
-# ---------------------------------------------------------------- 3: every kernel variant against clamp_ref
+# ---------------------------------------------------------------- 3: every kernel variant against the oracle
 
 K3, T3 = 1000, 9          # ragged K; T no multiple of the 4-deep ring and >= 5 for the device median
 _ref3 = {}
@@ -143,11 +99,12 @@ def _u3():
 
 
 def _reference3(lam, eps_tk, paths):
-    """clamp_ref on the read-back Philox noise of (seed 42, step 3), computed once per lambda and shared."""
+    """The oracle's clamped step on the read-back Philox noise of (seed 42, step 3), computed once per lambda and shared."""
     if lam not in _ref3:
-        _ref3[lam] = (eps_tk.copy(), CR.step(X0, _u3(), eps_tk.transpose(1, 0, 2).astype(np.float64),
-                                             paths["xydq_circle"], 0, 0.006, lam, 0.98, RUNPY["sigma"],
-                                             RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"], LO, HI))
+        _ref3[lam] = (eps_tk.copy(), O.step(X0, _u3(), eps_tk.transpose(1, 0, 2).astype(np.float64),
+                                            paths["xydq_circle"], 0, 0.006, lam, 0.98, RUNPY["sigma"],
+                                            RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"],
+                                            lo=LO, hi=HI))
     assert np.array_equal(_ref3[lam][0], eps_tk)
     return _ref3[lam][1]
 
@@ -167,7 +124,7 @@ def test_every_clamp_kernel_variant_against_clamp_ref(lps, handoff, lam, paths, 
     w_eps = eng.weighted_noise()
     S = S_dev.cpu().numpy()
     r = _reference3(lam, noise.cpu().numpy(), paths)
-    v = CR.sampled_controls(_u3(), noise.cpu().numpy().transpose(1, 0, 2), LO, HI)
+    v = O.sampled_controls(_u3(), noise.cpu().numpy().transpose(1, 0, 2), LO, HI)
     assert np.mean((v == LO) | (v == HI)) > 0.10             # the clamp is live at these limits
     print(f"lps {lps} {handoff} lam {lam}: S rel {float(np.max(np.abs(S - r['S']) / np.abs(r['S']))):.2e} "
           f"w_eps rel {_urel(w_eps, r['w_eps_raw']):.2e}")

@@ -29,20 +29,11 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from conftest import ctor_kwargs, load_loop, load_paths, load_step  # noqa: E402
+from helpers import RUNPY, _gpu, _urel  # noqa: E402, F401
 
 U_TOL = 1e-4
 X_TOL = 1e-10
-RUNPY = dict(param_exploration=0.0, param_lambda=100.0, param_alpha=0.98, sigma=np.eye(2) * 20.0,
-             stage_cost_weight=np.array([0.5, 0.5, 5.0, 5.0]),
-             terminal_cost_weight=np.array([5.0, 5.0, 50.0, 50.0]))
 DEV_K, DEV_T, DEV_TICKS, DEV_SEED = 8192, 32, 6, 3
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    torch.cuda.set_device(0)
 
 
 def _free_port():
@@ -51,10 +42,6 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
-
-
-def _urel(a, b):
-    return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
 
 
 # ---------------------------------------------------------------- scenarios

@@ -19,15 +19,9 @@ pytestmark = pytest.mark.gpu
 
 import philox_ref as P  # noqa: E402
 from conftest import record  # noqa: E402
+from helpers import _gpu  # noqa: E402, F401
 
 TOL = 2e-5
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    torch.cuda.set_device(0)
 
 
 @pytest.mark.parametrize("K_local,T,k_offset,seed,step", [(1000, 7, 0, 42, 3), (777, 1, 5000, 2 ** 40 + 9, 2 ** 33 + 1),

@@ -1,7 +1,7 @@
 """GPU: workspace obstacles (a collision cost on both links of the 2-link arm) through every layer.
 
 The fixtures are the reference's own outputs with only _c and _phi overridden (tests/golden/make_golden_obstacle.py);
-tests/obstacle_ref.py, pinned to them on the CPU (test_obstacle_cpu.py), is the yardstick at the other shapes.
+oracle/mppi_oracle.py with discs, pinned to them on the CPU (test_obstacle_cpu.py), is the yardstick at the other shapes.
 Tolerances are the suite's (test_gpu_parity.py): u 1e-4, S 5e-5 with the same argmin, w_eps 1e-10 on the sum
 recomputed on the host from the device's S.
 
@@ -19,10 +19,10 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import mppi_oracle as O  # noqa: E402
-import obstacle_ref as R  # noqa: E402
-from clamp_ref import CLAMP_STEPS, load_clamp_step  # noqa: E402
 from conftest import ctor_kwargs  # noqa: E402
-from obstacle_ref import OBST_STEPS, load_obst_loop, load_obst_step  # noqa: E402
+from helpers import (CLAMP_STEPS, OBST_STEPS, RUNPY, X0, _ctrl, _engine, _gpu, _urel, _window,  # noqa: E402, F401
+                     load_clamp_step, load_obst_loop, load_obst_step)
+from tieflip import waypoint_pick_delta  # noqa: E402
 
 U_TOL = 1e-4
 S_TOL = 5e-5
@@ -33,39 +33,9 @@ W_TOL = 1e-10
 EDGE = 4e-6
 EDGE_CAP = 0.005            # at most 0.5 % of the (sample, step) pairs may pass by that clause
 
-RUNPY = dict(param_exploration=0.0, param_lambda=100.0, param_alpha=0.98, sigma=np.eye(2) * 20.0,
-             stage_cost_weight=np.array([0.5, 0.5, 5.0, 5.0]),
-             terminal_cost_weight=np.array([5.0, 5.0, 50.0, 50.0]))
-X0 = np.array([1.152198236517471885e00, -1.266101672070702344e00, 0.0, 0.0])
 LO, HI = np.array([6.0, -5.0]), np.array([12.0, 1.0])
 LPS = (1, 2, 4, 8, 16)
 SHAPES = ((1000, 9), (300, 20))   # ragged K, more than one workgroup; T no multiple of the 4-deep ring, and one
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    torch.cuda.set_device(0)
-
-
-def _urel(a, b):
-    return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
-
-
-def _engine(K, T, lps=0, K_total=None, k_offset=0, u_min=None, u_max=None, **over):
-    from mppi_robotarm_amd.engine import RolloutEngine
-    from mppi_robotarm_amd.params import ArmParams
-    kw = dict(RUNPY)
-    kw.update(over)
-    return RolloutEngine(K, T, 0.006, kw["param_lambda"], kw["param_alpha"], kw["sigma"],
-                         kw["stage_cost_weight"], kw["terminal_cost_weight"], kw["param_exploration"],
-                         ArmParams(), K_total=K_total, k_offset=k_offset, device=0, lanes_per_sample=lps,
-                         u_min=u_min, u_max=u_max)
-
-
-def _window(paths, prev=0):
-    return paths["xydq_circle"][prev:prev + 30]
 
 
 def _u(T):
@@ -79,8 +49,9 @@ _prob = {}
 
 def _ref(K, T, paths, discs, w, lam=100.0, lo=None, hi=None, eps=None):
     p = _prob[(K, T)]
-    return R.rollout(X0, _u(T), p["eps"] if eps is None else eps, paths["xydq_circle"], 0, 0.006, lam, 0.98,
-                     RUNPY["sigma"], RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"], discs, w, lo, hi)
+    return O.rollout_costs(X0, _u(T), p["eps"] if eps is None else eps, paths["xydq_circle"], 0, 0.006, lam, 0.98,
+                           RUNPY["sigma"], RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"], lo=lo, hi=hi,
+                           discs=discs, obstacle_cost=w, details=True)
 
 
 def _problem(K, T, paths):
@@ -141,8 +112,8 @@ def test_flag_parity_on_the_devices_own_directions(K, T, n, paths):
     q = p["free"]["q"]
     want = np.stack([np.cos(q[..., 0]), np.sin(q[..., 0]), np.cos(q.sum(-1)), np.sin(q.sum(-1))], -1)
     assert float(np.max(np.abs(d - want))) < 1e-4
-    dist, _ = R.segment_test(d[..., 0], d[..., 1], d[..., 2], d[..., 3], discs, 1.0, 1.0)
-    want_mask = R.touch_mask(dist, discs)
+    dist, _ = O.segment_test(d[..., 0], d[..., 1], d[..., 2], d[..., 3], discs, 1.0, 1.0)
+    want_mask = O.touch_mask(dist, discs)
     r = discs[:, 2]
     per_bit_clear = np.abs(dist - r[:, None])                                    # (K, T, n, 2)
     bits = (np.uint32(1) << np.arange(2 * n, dtype=np.uint32)).reshape(n, 2)
@@ -254,7 +225,7 @@ def _with_device_hits(K, T, paths, discs, w, lam, hits, lo=None, hi=None):
     p = _prob[(K, T)]
     r = _ref(K, T, paths, discs, w, lam, lo, hi)
     S = r["S_track"] + w * hits
-    return {**r, "S": S, **R.update(S, _u(T), p["eps"], lam, X0, 0.006, lo, hi)}
+    return {**r, "S": S, **O.update(S, _u(T), p["eps"], lam, X0, 0.006, lo, hi)}
 
 
 @pytest.mark.parametrize("lam,w", [(100.0, 1.0e10), (3.0e6, 3.0e6)])
@@ -320,18 +291,6 @@ def test_two_shards_merge_to_the_unsharded_launch(paths):
 
 # ---------------------------------------------------------------- 5: the fixtures through the drop-in
 
-def _ctrl(g, paths, **kw):
-    from mppi_robotarm_amd.controller import MPPIControllerForPathTracking
-    lim = dict(u_min=g["u_min"], u_max=g["u_max"]) if "u_min" in g else {}
-    c = MPPIControllerForPathTracking(ref_path=paths[str(g["path"])], verbose=False,
-                                      visualize_optimal_traj=bool(g["visualize_optimal_traj"]),
-                                      obstacles=g["obstacles"], obstacle_cost=float(g["obstacle_cost"]),
-                                      **lim, **ctor_kwargs(g), **kw)
-    c.prev_waypoints_idx = int(g["prev_idx"])
-    c.u_prev = g["u_prev"].copy()
-    return c
-
-
 def _feed(c, eps, how):
     if how == "tick":
         eng = c._get_engine()
@@ -372,12 +331,13 @@ def test_obstructed_step_matches_reference(name, how, paths):
     else:
         # dense weights: a sample on the other side of a boundary moves its weight by e^(-w / lambda); the yardstick
         # takes the device's own hit counts (S_dev - S_track, exact multiples of w) so a tie cannot move one
-        r = R.rollout(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]), float(g["delta_t"]),
-                      float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"], g["stage_cost_weight"],
-                      g["terminal_cost_weight"], g["obstacles"], float(g["obstacle_cost"]))
+        r = O.rollout_costs(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]),
+                            float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
+                            g["stage_cost_weight"], g["terminal_cost_weight"], discs=g["obstacles"],
+                            obstacle_cost=float(g["obstacle_cost"]), details=True)
         hits = np.rint((c.last_S - r["S_track"]) / float(g["obstacle_cost"]))
         assert float(np.mean(hits == r["hits"])) >= 0.99
-        up = R.update(r["S_track"] + float(g["obstacle_cost"]) * hits, g["u_prev"], eps, float(g["param_lambda"]),
+        up = O.update(r["S_track"] + float(g["obstacle_cost"]) * hits, g["u_prev"], eps, float(g["param_lambda"]),
                       g["x0"], float(g["delta_t"]))
         assert _urel(u_seq, up["u_seq"]) < U_TOL
     c.close()
@@ -420,10 +380,11 @@ def test_obstructed_closed_loop_ticks(paths):
         window = paths["xydq_circle"][c.prev_waypoints_idx:c.prev_waypoints_idx + 30]
         c._engine.set_step_inputs(g["states"][i], window, u_prev)
         slots, _ = c._engine.nearest_slots(c._noise_dev)
-        r = R.rollout(g["states"][i], u_prev, eps, paths["xydq_circle"], c.prev_waypoints_idx, 0.006, 100.0, 0.98,
-                      RUNPY["sigma"], RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"], g["obstacles"], w)
-        delta, gap, differ = R.waypoint_pick_delta(r, slots, window, RUNPY["stage_cost_weight"],
-                                                   RUNPY["terminal_cost_weight"])
+        r = O.rollout_costs(g["states"][i], u_prev, eps, paths["xydq_circle"], c.prev_waypoints_idx, 0.006, 100.0,
+                            0.98, RUNPY["sigma"], RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"],
+                            discs=g["obstacles"], obstacle_cost=w, details=True)
+        delta, gap, differ = waypoint_pick_delta(r, slots, window, RUNPY["stage_cost_weight"],
+                                                 RUNPY["terminal_cost_weight"])
         ref = g["S"][i] + delta
         plain = float(np.max(np.abs(S[clean] - g["S"][i][clean]) / np.abs(g["S"][i][clean])))
         rel = float(np.max(np.abs(S[clean] - ref[clean]) / np.abs(ref[clean])))
@@ -553,7 +514,7 @@ def test_decomposition_with_torque_limits(lps, paths):
     eng.rollout(noise, fused_update=True)
     u = eng.nominal()
     assert bool(np.all((u >= LO) & (u <= HI)))               # the nominal's clamp still runs (mode 2)
-    up = R.update(r_["S_track"] + w * hits, _u(T), p["eps"], 100.0, X0, 0.006, LO, HI)
+    up = O.update(r_["S_track"] + w * hits, _u(T), p["eps"], 100.0, X0, 0.006, LO, HI)
     assert _urel(u, up["u_seq"]) < U_TOL
     eng.close()
 

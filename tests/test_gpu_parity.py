@@ -17,44 +17,12 @@ pytestmark = pytest.mark.gpu
 
 import coracle  # noqa: E402
 import mppi_oracle as O  # noqa: E402
-from conftest import LOOP_FIXTURES, STEP_FIXTURES, ctor_kwargs, load_loop, load_step, record  # noqa: E402
+from conftest import LOOP_FIXTURES, STEP_FIXTURES, load_loop, load_step, record  # noqa: E402
+from helpers import RUNPY, X0, _ctrl, _engine, _gpu, _urel, _window  # noqa: E402, F401
 
 U_TOL = 1e-4
 S_TOL = 5e-5
 
-RUNPY = dict(param_exploration=0.0, param_lambda=100.0, param_alpha=0.98, sigma=np.eye(2) * 20.0,
-             stage_cost_weight=np.array([0.5, 0.5, 5.0, 5.0]),
-             terminal_cost_weight=np.array([5.0, 5.0, 50.0, 50.0]))
-X0 = np.array([1.152198236517471885e00, -1.266101672070702344e00, 0.0, 0.0])
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    torch.cuda.set_device(0)
-
-
-def _ctrl(g, paths, **kw):
-    from mppi_robotarm_amd.controller import MPPIControllerForPathTracking
-    c = MPPIControllerForPathTracking(ref_path=paths[str(g["path"])], verbose=False, **ctor_kwargs(g), **kw)
-    c.prev_waypoints_idx = int(g["prev_idx"])
-    c.u_prev = g["u_prev"].copy()
-    return c
-
-
-def _urel(a, b):
-    return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
-
-
-def _engine(K, T, lps=0, K_total=None, k_offset=0, **over):
-    from mppi_robotarm_amd.engine import RolloutEngine
-    from mppi_robotarm_amd.params import ArmParams
-    kw = dict(RUNPY)
-    kw.update(over)
-    return RolloutEngine(K, T, 0.006, kw["param_lambda"], kw["param_alpha"], kw["sigma"],
-                         kw["stage_cost_weight"], kw["terminal_cost_weight"], kw["param_exploration"],
-                         ArmParams(), K_total=K_total, k_offset=k_offset, device=0, lanes_per_sample=lps)
 
 
 @pytest.mark.parametrize("name", STEP_FIXTURES)
@@ -113,10 +81,6 @@ def test_closed_loop_ticks(name, paths):
         assert c.prev_waypoints_idx == int(g["prev_idx"][i])
         u_prev, prev = g["u_seq"][i].copy(), int(g["prev_idx"][i])
     c.close()
-
-
-def _window(paths, prev=0):
-    return paths["xydq_circle"][prev:prev + 30]
 
 
 @pytest.mark.parametrize("K,T,lam,lps", [(65536, 64, 100.0, 0), (65536, 64, 3.0e6, 0), (65536, 64, 100.0, 2),

@@ -1,6 +1,6 @@
 """CPU: workspace obstacles (a collision cost on both links of the 2-link arm).
 
-  * tests/obstacle_ref.py, the NumPy restatement the GPU tests use as their yardstick, is pinned to every
+  * oracle/mppi_oracle.py with discs, the NumPy restatement the GPU tests use as their yardstick, is pinned to every
     obst_step_* / obst_loop_* fixture captured from the reference itself (make_golden_obstacle.py: the reference
     with only _c and _phi overridden): S to 1e-12 relative, every collision flag equal, the clearance, and the
     returned controls bit for bit where the weights are one-hot;
@@ -16,21 +16,22 @@ import subprocess
 import numpy as np
 import pytest
 
-import obstacle_ref as R
+import mppi_oracle as O
 from conftest import GOLDEN, ROOT
+from helpers import OBST_STEPS, load_obst_loop, load_obst_step
 from mppi_robotarm_amd.controller import MPPIControllerForPathTracking
 from mppi_robotarm_amd.engine import RolloutEngine
-from obstacle_ref import OBST_STEPS, load_obst_loop, load_obst_step
 
 HEADER = os.path.join(ROOT, "include", "mppi_rocm.h")
 
 
 def ref_step(g, path, discs=None, w=None):
-    return R.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), path, int(g["prev_idx_after"]),
+    return O.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), path, int(g["prev_idx_after"]),
                   float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
                   g["stage_cost_weight"], g["terminal_cost_weight"],
-                  g["obstacles"] if discs is None else discs, float(g["obstacle_cost"]) if w is None else w,
-                  g.get("u_min"), g.get("u_max"), expl=float(g["param_exploration"]),
+                  discs=g["obstacles"] if discs is None else discs,
+                  obstacle_cost=float(g["obstacle_cost"]) if w is None else w,
+                  lo=g.get("u_min"), hi=g.get("u_max"), expl=float(g["param_exploration"]),
                   visualize_optimal_traj=bool(g["visualize_optimal_traj"]))
 
 
@@ -95,9 +96,10 @@ def test_obstacle_ref_matches_the_reference_closed_loop(paths):
     assert 0.10 <= float(np.mean(g["flag"].any(2))) <= 0.90
     assert not np.allclose(g["u"], g["u_free"])
     for i in range(int(g["ticks"])):
-        r = R.step(g["states"][i], u_prev, g["eps"][i].astype(np.float64), paths["xydq_circle"],
+        r = O.step(g["states"][i], u_prev, g["eps"][i].astype(np.float64), paths["xydq_circle"],
                    int(g["prev_idx"][i]), 0.006, kw["param_lambda"], kw["param_alpha"], kw["sigma"],
-                   kw["stage_cost_weight"], kw["terminal_cost_weight"], g["obstacles"], float(g["obstacle_cost"]))
+                   kw["stage_cost_weight"], kw["terminal_cost_weight"], discs=g["obstacles"],
+                   obstacle_cost=float(g["obstacle_cost"]))
         assert np.array_equal(r["flag"], g["flag"][i]), i
         assert float(np.max(np.abs(r["S"] - g["S"][i]) / np.abs(g["S"][i]))) < 1e-12, i
         np.testing.assert_allclose(r["u_seq"], g["u_seq"][i], rtol=1e-10, atol=1e-10)
@@ -113,7 +115,7 @@ def test_segment_geometry():
                       [1.0, 1.25, 0.3],     # above link 2's tip: clipped to s = L, d = 0.25
                       [1.2, 0.5, 0.2],      # beside link 2: d = 0.2, not < r: the boundary does not touch
                       [1.2, 0.5, 0.2000001]])
-    flag, clear, dist, clipped = R.collides(np.array(0.0), np.array(np.pi / 2), discs)
+    flag, clear, dist, clipped = O.collides(np.array(0.0), np.array(np.pi / 2), discs)
     np.testing.assert_allclose(dist[:, 0], [0.05, 0.3, 0.1, 1.25, np.hypot(0.2, 0.5), np.hypot(0.2, 0.5)], atol=1e-12)
     np.testing.assert_allclose(dist[3, 1], 0.25, atol=1e-12)
     np.testing.assert_allclose(dist[4:, 1], [0.2, 0.2], atol=1e-12)
@@ -122,9 +124,9 @@ def test_segment_geometry():
     assert hit[:, 1].tolist() == [False, False, False, True, bool(dist[4, 1] < 0.2), True]
     assert clipped[:, 0].tolist() == [False, True, True, False, True, True]
     assert bool(clipped[3, 1]) and not bool(clipped[4, 1])
-    assert R.touch_mask(dist, discs) == sum(1 << (2 * j + l) for j in range(6) for l in range(2) if hit[j, l])
+    assert O.touch_mask(dist, discs) == sum(1 << (2 * j + l) for j in range(6) for l in range(2) if hit[j, l])
     assert bool(flag)
-    none = R.collides(np.array(0.0), np.array(np.pi / 2), np.zeros((0, 3)))
+    none = O.collides(np.array(0.0), np.array(np.pi / 2), np.zeros((0, 3)))
     assert not bool(none[0]) and np.isinf(none[1])
 
 

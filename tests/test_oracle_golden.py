@@ -10,10 +10,7 @@ import pytest
 import coracle
 import mppi_oracle as O
 from conftest import GOLDEN, LOOP_FIXTURES, STEP_FIXTURES, ctor_kwargs, load_loop, load_step
-
-RUNPY = dict(param_exploration=0.0, param_lambda=100.0, param_alpha=0.98, sigma=np.eye(2) * 20.0,
-             stage_cost_weight=np.array([0.5, 0.5, 5.0, 5.0]),
-             terminal_cost_weight=np.array([5.0, 5.0, 50.0, 50.0]))
+from helpers import RUNPY
 
 
 def _run_oracle(g, paths):

@@ -17,12 +17,14 @@ the gaps used are below the fp32 position resolution of the trajectory.
 can record the slot it picked at every step (ChainEngine.debug_slots): the fp64
 cost recomputed with the device's own picks, and the gap at every step where a
 pick differs from the fp64 argmin — no search over flip combinations.
+``waypoint_pick_delta`` is the same for the 2-link arm (RolloutEngine.nearest_slots).
 """
 from __future__ import annotations
 
 import numpy as np
 
 import chain_oracle as CO
+import mppi_oracle as O
 
 
 def tie_table(idx, x0, u, eps_tnk, win, dt, stage_w, term_w, P, exploit=None):
@@ -105,6 +107,33 @@ def device_pick_residual(S_dev, S_ref, idx, x0, u, eps_tnk, win, dt, stage_w, te
         ndiff += diff
     res = np.abs(np.asarray(S_dev, dtype=np.float64)[idx] - alt) / np.abs(alt)
     return res, gap, ndiff
+
+
+def waypoint_pick_delta(r, slots, window, stage_w, term_w):
+    """device_pick_residual's accounting for the 2-link arm.  Where the fp64 end effector lies within fp32
+    resolution of the bisector between two window slots, the device may pick the neighbour; the states do not
+    depend on the pick, so S then differs by exactly those steps' cost difference between the two slots.  From
+    O.rollout_costs(details=True)'s dict `r` and the device's own picks `slots` (K, T) (mppi_debug_nearest):
+    (delta (K,) to add to the fp64 S, gap (K, T) the distance to the picked slot minus the distance to the fp64
+    nearest, 0 where the picks agree, differ (K, T) bool)."""
+    win = np.asarray(window, dtype=np.float64)
+    x, y, dq = r["ee"][..., 0], r["ee"][..., 1], r["dq"]
+    d = (x[..., None] - win[:, 0]) ** 2 + (y[..., None] - win[:, 1]) ** 2
+    j1 = O.first_min_index(d * 100)
+    jd = np.asarray(slots, dtype=np.int64)
+    T = x.shape[1]
+    w = np.tile(np.asarray(stage_w, dtype=np.float64), (T, 1))
+    w[-1] += np.asarray(term_w, dtype=np.float64)          # the terminal cost takes the same slot
+
+    def cost(j):
+        ref = win[j]
+        return 10000 * (w[:, 0] * (x - ref[..., 0]) ** 2 + w[:, 1] * (y - ref[..., 1]) ** 2 +
+                        w[:, 2] * (dq[..., 0] - ref[..., 2]) ** 2 + w[:, 3] * (dq[..., 1] - ref[..., 3]) ** 2)
+
+    differ = jd != j1
+    delta = np.where(differ, cost(jd) - cost(j1), 0.0).sum(1)
+    take = lambda j: np.sqrt(np.take_along_axis(d, j[..., None], -1)[..., 0])   # noqa: E731
+    return delta, np.where(differ, take(jd) - take(j1), 0.0), differ
 
 
 def tie_flip_residual(S_dev, S_ref, idx, x0, u, eps_tnk, win, dt, stage_w, term_w, P, exploit=None,
