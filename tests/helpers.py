@@ -1,5 +1,5 @@
-"""What the test files share besides conftest.py's fixtures: the clamp_* / obst_* fixture plumbing, run.py's
-constants, and the GPU tests' helpers (torch and the package are imported inside the functions, so this module
+"""What the test files share besides conftest.py's fixtures: the clamp_* / obst_* / asym_* fixture plumbing, run.py's
+constants, the asymmetric arm cases and non-uniform chains, and the GPU tests' helpers (torch and the package are imported inside the functions, so this module
 imports without either).
 
 The yardsticks themselves live in ``oracle/``: ``mppi_oracle.py`` (the arm, with torque limits and workspace
@@ -38,6 +38,17 @@ def load_obst_step(name):
 
 def load_obst_loop(name):
     return dict(np.load(os.path.join(GOLDEN, f"obst_loop_{name}.npz")))
+
+
+ASYM_STEPS = _names("asym_step_")
+
+
+def load_asym_step(name):
+    return dict(np.load(os.path.join(GOLDEN, f"asym_step_{name}.npz")))
+
+
+def load_asym_loop(name):
+    return dict(np.load(os.path.join(GOLDEN, f"asym_loop_{name}.npz")))
 
 
 RUNPY = dict(param_exploration=0.0, param_lambda=100.0, param_alpha=0.98, sigma=np.eye(2) * 20.0,
@@ -94,3 +105,120 @@ def _ctrl(g, paths, **kw):
     c.prev_waypoints_idx = int(g["prev_idx"])
     c.u_prev = g["u_prev"].copy()
     return c
+
+
+# ---------------------------------------------------------------- asymmetric parameters (tests/golden/make_golden_asym.py)
+
+ARM_FIELDS = ("m1", "m2", "l1", "l2", "lc1", "lc2", "g", "fk_l1", "fk_l2")
+# the arm cases the GPU tests run besides the fixtures themselves: (fixture whose parameter set, pose and window it
+# takes, K, T) at the smallest shapes that reach every code path (test_gpu_obstacles.py's)
+ASYM_SHAPES = ((1000, 9), (300, 20))
+ASYM_CASES = [(name, K, T) for name in ("a_k128_t20", "b_dense_k256_t24", "c_elbowup_k128_t20")
+              for K, T in ASYM_SHAPES]
+# Set b's alpha = 0.9 at lambda = 3e6 makes gamma = 3e5: the control-cost term, which the device computes in fp64 from
+# the noise it is given, is then 99.9 % of S and hides the dynamics and the state cost from any relative tolerance.
+# The fixture keeps alpha = 0.9 (through the drop-in); the rollout cases take alpha = 1.
+ASYM_OVER = {"b_dense_k256_t24": dict(param_alpha=0.99999)}
+
+
+def arm_of(g, cls):
+    """The ArmParams (oracle's or package's class) stored in an asym_* fixture."""
+    return cls(**{f: float(g[f]) for f in ARM_FIELDS})
+
+
+def asym_cfg(g):
+    """The controller constants of an asym_* fixture (either kind)."""
+    return dict(delta_t=float(g["delta_t"]), param_lambda=float(g["param_lambda"]), param_alpha=float(g["param_alpha"]),
+                param_exploration=float(g["param_exploration"]), sigma=g["sigma"],
+                stage_cost_weight=g["stage_cost_weight"], terminal_cost_weight=g["terminal_cost_weight"])
+
+
+def asym_problem(name, T):
+    """Fixture `name`'s constants, start state and window with a nominal of horizon T: the fixture's gravity-holding
+    row plus seeded noise.  Returns (g, cfg, x0, prev, u)."""
+    g = load_asym_step(name)
+    g.update({k: np.float64(v) for k, v in ASYM_OVER.get(name, {}).items()})
+    u = np.tile(g["u_prev"][0], (T, 1)) + np.random.default_rng(T).normal(0, 0.5, (T, 2))
+    return g, asym_cfg(g), g["x0"], int(g["prev_idx_after"]), u
+
+
+def asym_engine(g, K, T, lps=0, K_total=None, k_offset=0, u_min=None, u_max=None, **over):
+    """The arm's engine at an asym_* fixture's constants, `over` replacing any of asym_cfg's."""
+    from mppi_robotarm_amd.engine import RolloutEngine
+    from mppi_robotarm_amd.params import ArmParams
+    kw = asym_cfg(g)
+    kw.update(over)
+    return RolloutEngine(K, T, kw["delta_t"], kw["param_lambda"], kw["param_alpha"], kw["sigma"],
+                         kw["stage_cost_weight"], kw["terminal_cost_weight"], kw["param_exploration"],
+                         arm_of(g, ArmParams), K_total=K_total, k_offset=k_offset, device=0, lanes_per_sample=lps,
+                         u_min=u_min, u_max=u_max)
+
+
+# (n, K, T, lambda) of the non-uniform chains on the GPU (test_gpu_chain_asym.py): test_gpu_chain.LINK_CASES' shapes.
+# lambda = 100 at n = 7 too: at LINK_CASES' 1e8 the control-cost term is all of S and no link constant shows.
+ASYM_LINK_CASES = [(3, 256, 16, 100.0), (4, 3000, 24, 100.0), (5, 777, 32, 1.0e4), (6, 2048, 20, 100.0),
+                   (7, 1000, 9, 100.0), (2, 513, 40, 100.0)]
+
+
+def asym_chain_kwargs(n):
+    """A non-uniform n-link chain, seeded per n: every entry of m, l, lc, I, fk, J, b differs from every other entry
+    of its vector (a permuted ramp), total reach 2 m, armature and damping spread over a decade."""
+    rng = np.random.default_rng(7000 + n)
+    ramp = lambda lo, hi: rng.permutation(np.linspace(lo, hi, n))   # noqa: E731
+    l = ramp(0.7, 1.3)
+    l = l * 2.0 / l.sum()
+    return dict(m=tuple(ramp(0.6, 1.4)), l=tuple(l), lc=tuple(l * ramp(0.35, 0.6)), I=tuple(ramp(0.01, 0.12)),
+                fk=tuple(l * ramp(0.75, 1.2)), J=tuple(ramp(0.02, 0.4)), b=tuple(ramp(0.2, 3.0)))
+
+
+def asym_chain_inputs(n, T, mod):
+    """asym_chain_kwargs(n) as `mod`.ChainParams (the oracle's module or the package's), a start state with joint
+    rates around 1 rad/s, a random SPD Sigma and a gravity-holding nominal plus noise."""
+    import chain_oracle as CO
+    rng = np.random.default_rng(n * 100 + T + 7)
+    kw = asym_chain_kwargs(n)
+    q = np.array([1.4] + [-2.2 / (n - 1)] * (n - 1))
+    x0 = np.concatenate([q, rng.uniform(0.6, 1.4, n) * rng.choice([-1.0, 1.0], n)])
+    A = rng.normal(0, 1, (n, n))
+    sig = A @ A.T / n + np.diag(np.linspace(8.0, 1.0, n))
+    u = np.tile(CO.gravity_torque(q, CO.ChainParams(**kw)), (T, 1)) + rng.normal(0, 0.3, (T, n))
+    return mod.ChainParams(**kw), x0, sig, u
+
+
+def asym_rollout(g, cfg, x0, prev, u, eps, paths, **kw):
+    """The fp64 yardstick's rollout (details=True) at an asym_* fixture's constants; eps (K, T, 2)."""
+    import mppi_oracle as O
+    return O.rollout_costs(x0, u, eps, paths["xydq_circle"], prev, cfg["delta_t"], cfg["param_lambda"],
+                           cfg["param_alpha"], cfg["sigma"], cfg["stage_cost_weight"], cfg["terminal_cost_weight"],
+                           cfg["param_exploration"], arm_of(g, O.ArmParams), details=True, **kw)
+
+
+def asym_obstacle_problem(g, cfg, x0, prev, u, eps, paths):
+    """Discs that tell the cost's two link lengths apart (fk_l1 = 1.1, fk_l2 = 0.9), placed from the yardstick's own
+    unobstructed rollout on eps (over a short horizon the arm moves millimetres: a disc anywhere else is never
+    touched).  With s the spread of link 1's final angle:
+      0. beside link 1's last 5 cm, 2.5 cm short of the elbow on the side away from link 2, radius 4 s: the 30 % of
+         the samples whose link 1 turned furthest that way touch it; a link 1 of 0.9 ends 17 cm short of it;
+      1. 3 cm past link 2's tip along the link, radius 1.5 cm: never touched, but a link 2 of 1.1 runs through it;
+      2. at the elbow, its centre 0.8 r beside link 1's end on that same side (behind link 2's start), radius
+         r = 0.4 s: the clipped ends of both links touch it in a band of samples above the 8 % quantile of the other
+         tail (the start pose, from which the samples spread, stays outside the band);
+      3. behind the base, 4 mm short of link 1's clipped start: never touched.
+    Returns dict(free=the rollout, discs=(4, 3))."""
+    free = asym_rollout(g, cfg, x0, prev, u, eps, paths)
+    a, b = float(g["fk_l1"]), float(g["fk_l2"])
+    q1, q12 = free["q"][:, -1, 0], free["q"][:, -1].sum(-1)
+    side = 1.0 if float(np.median(free["q"][:, -1, 1])) < 0 else -1.0
+    s = float(np.std(q1))
+    unit = lambda t: np.array([np.cos(t), np.sin(t)])           # noqa: E731
+    normal = lambda t: np.array([-np.sin(t), np.cos(t)])        # noqa: E731
+    th = float(np.quantile(q1, 0.7 if side > 0 else 0.3))
+    d = a - 0.025
+    r0 = max(4.0 * d * s, 1e-4)
+    c0 = d * unit(th) + side * r0 * normal(th)
+    c1 = a * unit(float(np.median(q1))) + (b + 0.03) * unit(float(np.median(q12)))
+    te = float(np.quantile(q1, 0.08 if side > 0 else 0.92))
+    r2 = max(0.4 * a * s, 1e-4)
+    c2 = a * unit(te) + side * 0.8 * r2 * normal(te)
+    discs = np.array([[c0[0], c0[1], r0], [c1[0], c1[1], 0.015], [c2[0], c2[1], r2], [-0.05, -0.02, 0.05]])
+    return dict(free=free, discs=discs)
