@@ -51,6 +51,13 @@ extern "C" {
 #define MPPI_FLAG_HOST_OUT 4u      /* with FUSED_UPDATE: the final workgroup also writes   */
                                    /* the shifted nominal to host-mapped memory; read it  */
                                    /* with mppi_wait_outputs (no copy, no stream sync)    */
+#define MPPI_FLAG_INLINE_MERGE 8u   /* with FUSED_UPDATE alone: finish the step inside the  */
+                                   /* launch.  Without it such a launch may end at its     */
+                                   /* workgroup rows and leave the merge and the update to */
+                                   /* the next launch's prologue (the deferred form of the */
+                                   /* device-resident loop, same bits); the context then   */
+                                   /* finishes the step itself before any call that reads  */
+                                   /* or replaces its result (see mppi_rollout)            */
 #define MPPI_IPC_HANDLE_BYTES 64   /* hipIpcMemHandle_t                                    */
 #define MPPI_MAX_WORLD 8           /* ranks of one node for the in-launch exchange         */
 
@@ -127,6 +134,10 @@ int mppi_ctx_info(const mppi_ctx *ctx, int *lanes_per_sample, int *blocks, int *
  * control.py:112-118). */
 int mppi_ctx_handoff(const mppi_ctx *ctx, int *poll);
 
+/* Diagnostics: *pending = 1 while the last fused launch took the deferred form
+ * and its step is not finished yet (see mppi_rollout), else 0. */
+int mppi_debug_pending(const mppi_ctx *ctx, int *pending);
+
 /* Per control step inputs (control.py:70-75): observed state x0[4], the search
  * window ref_path[prev:prev+W, 0:4] (W = min(30, N - prev), row-major W x 4),
  * and the nominal control sequence u[T][2] (self.u_prev).  x0 and the window
@@ -146,6 +157,22 @@ int mppi_set_step_inputs(mppi_ctx *ctx, const double *x0, const double *window, 
  *               rho = min S, eta = sum exp(-(S-rho)/lambda), N = sum exp(.) eps —
  *               the operand of the cross-device exchange;
  *   flags       MPPI_FLAG_FUSED_UPDATE: finish the step on device (single device).
+ *               With that flag alone, no partial_dev, a stream that is not being
+ *               captured and a grid of at most 256 workgroups, the launch takes
+ *               the deferred form: it ends at its workgroup rows, and the next
+ *               such launch merges them and updates the nominal in its prologue,
+ *               in every workgroup, before it rolls out (bit-identical to the
+ *               in-launch finish).  A step left pending is finished by a
+ *               one-workgroup launch before mppi_get_weighted_noise,
+ *               mppi_get_nominal, mppi_get_step_outputs, mppi_set_step_inputs
+ *               with a nominal, any other form of mppi_rollout,
+ *               mppi_merge_partials, mppi_rollout_traj, mppi_optimal_traj,
+ *               the mppi_debug_* kernels, mppi_set_stream, mppi_sync and
+ *               mppi_ctx_destroy; the device buffers hold its result only
+ *               after one of these.  MPPI_FLAG_INLINE_MERGE forces the
+ *               in-launch finish.  Do not begin a graph capture on the
+ *               context's stream between a deferred launch and one of these
+ *               calls (MPPI_E_ARG).
  * The weighted noise w_eps = N / eta (control.py:112-118) is left in the
  * context (mppi_get_weighted_noise). */
 int mppi_rollout(mppi_ctx *ctx, const float *noise_dev, double *S_dev, double *partial_dev,

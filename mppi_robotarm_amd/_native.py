@@ -24,6 +24,7 @@ MPPI_E_RETRY = -6
 MPPI_FLAG_FUSED_UPDATE = 1
 MPPI_FLAG_EXCHANGE = 2
 MPPI_FLAG_HOST_OUT = 4
+MPPI_FLAG_INLINE_MERGE = 8
 DP = C.POINTER(C.c_double)
 MPPI_IPC_HANDLE_BYTES = 64
 MPPI_MAX_WORLD = 8
@@ -38,7 +39,7 @@ EXPORTS = (
     "mppi_optimal_traj_host", "mppi_wait_outputs", "mppi_dropin_bind", "mppi_dropin_tick",
     "mppi_dropin_tick_launch", "mppi_dropin_tick_wait",
     "mppi_noise_philox",
-    "mppi_sync", "mppi_debug_set_buffer",
+    "mppi_sync", "mppi_debug_set_buffer", "mppi_debug_pending",
     "mppi_debug_nearest", "mppi_debug_dropin_times", "mppi_set_obstacles", "mppi_debug_obstacle_hits",
     "mppi_chain_ctx_create", "mppi_chain_ctx_destroy", "mppi_chain_set_stream", "mppi_chain_ctx_info",
     "mppi_chain_set_step_inputs", "mppi_chain_rollout", "mppi_chain_merge_partials", "mppi_chain_exchange_handle",
@@ -151,6 +152,7 @@ def open_library(path: str):
         "mppi_set_stream": ([vp, vp], C.c_int),
         "mppi_ctx_info": ([vp, ip, ip, ip], C.c_int),
         "mppi_ctx_handoff": ([vp, ip], C.c_int),
+        "mppi_debug_pending": ([vp, ip], C.c_int),
         "mppi_set_step_inputs": ([vp, dp, dp, C.c_int, dp], C.c_int),
         "mppi_rollout": ([vp, fp, vp, vp, C.c_uint], C.c_int),
         "mppi_merge_partials": ([vp, vp, C.c_int, C.c_uint], C.c_int),

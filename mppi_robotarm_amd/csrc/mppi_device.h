@@ -378,6 +378,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(const void* p, int b
 __device__ __forceinline__ double ld_wt(__amdgpu_buffer_rsrc_t r, int idx) {
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, idx * 8, 0, kSC1));
 }
+// A row value of the PREVIOUS launch (the deferred finish): visible since the kernel boundary, so an ordinary
+// cached load; the workgroups of an XCD, which all read the same rows, share its L2 lines.
+__device__ __forceinline__ double ld_prev(__amdgpu_buffer_rsrc_t r, int idx) {
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, idx * 8, 0, 0));
+}
 __device__ __forceinline__ void st_wt(__amdgpu_buffer_rsrc_t r, int idx, double v) {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, idx * 8, 0, kSC1);
 }
@@ -668,11 +673,16 @@ __device__ __forceinline__ void merge_rows_block(__amdgpu_buffer_rsrc_t rows, in
 // on the critical path instead of two.  Returns false (uniformly) when more rows
 // carry weight; the caller then merges through the group rows.  Wave-local
 // like merge_rows_block; the result goes out as in a final merge.
-template <int NT, int MAXCH, bool GRAN, class SM>
+// PRE: the caller has loaded the rows' rho already (rho_pre: row lane + 64 j in slot j, INFINITY past n).
+template <int NT, int MAXCH, bool GRAN, bool PRE = false, class SM>
 __device__ __forceinline__ bool direct_merge(__amdgpu_buffer_rsrc_t rows, int n, const RowGeo& geo,
                                              double inv_lambda, SM& sm, double* out_row, double* w_eps_out,
-                                             unsigned tag, unsigned* tmo, unsigned long long* dbg = nullptr) {
+                                             unsigned tag, unsigned* tmo, unsigned long long* dbg = nullptr,
+                                             const double* rho_pre = nullptr) {
     constexpr int P = kDirectRows / 64;
+    static_assert(!(PRE && GRAN), "granules are polled here");
+    // the rows of this launch travel write-through (sc1); PRE: the previous launch's, through the caches
+    auto ld = [](__amdgpu_buffer_rsrc_t r, int idx) { return PRE ? ld_prev(r, idx) : ld_wt(r, idx); };
     constexpr int LB = 16;                      // loads per batch per thread
     constexpr int RB = LB / MAXCH;              // rows per load batch
     const int tid = threadIdx.x, lane = tid & 63;
@@ -702,6 +712,9 @@ __device__ __forceinline__ bool direct_merge(__amdgpu_buffer_rsrc_t rows, int n,
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < P; ++j) rho_l[j] = sm.rho[lane + 64 * j];
+    } else if constexpr (PRE) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) rho_l[j] = rho_pre[j];
     } else {
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -783,12 +796,12 @@ __device__ __forceinline__ bool direct_merge(__amdgpu_buffer_rsrc_t rows, int n,
 #pragma unroll
                 for (int j = 0; j < LB; ++j) v[j] = gran_val(gv[j]);
             } else {
-                if (b0 == 0) eta_k = ld_wt(rows, mine ? row * stride + 1 : kOffRange);
+                if (b0 == 0) eta_k = ld(rows, mine ? row * stride + 1 : kOffRange);
 #pragma unroll
                 for (int j = 0; j < LB; ++j) {
                     const int i = b0 + j / MAXCH, col = tid + (j % MAXCH) * NT;
-                    v[j] = ld_wt(rows, (i < nrel && col < ncol) ? __builtin_amdgcn_readlane(row, i) * stride + 1 + col
-                                                                 : kOffRange);
+                    v[j] = ld(rows, (i < nrel && col < ncol) ? __builtin_amdgcn_readlane(row, i) * stride + 1 + col
+                                                              : kOffRange);
                 }
             }
 #pragma unroll
@@ -837,7 +850,7 @@ __device__ __forceinline__ bool direct_merge(__amdgpu_buffer_rsrc_t rows, int n,
                 for (int j = 0; j < LB; ++j) v[j] = gran_val(gv[j]);
             } else {
 #pragma unroll
-                for (int j = 0; j < LB; ++j) v[j] = ld_wt(rows, roff[j]);
+                for (int j = 0; j < LB; ++j) v[j] = ld(rows, roff[j]);
             }
 #pragma unroll
             for (int j = 0; j < LB; ++j)
@@ -1017,6 +1030,108 @@ __device__ __forceinline__ bool handoff_merge(__amdgpu_buffer_rsrc_t slab_r, __a
                                                      w_eps_out, 0u, nullptr);
     }
     return true;
+}
+
+// The same merge one launch later (the deferred finish of the 2-DoF device loop, mppi_rocm.hip): the n <=
+// kDirectRows rows of the PREVIOUS launch, plain 8-byte values that became visible at the kernel boundary, merged
+// by every workgroup for itself.  No poll, no tag, no counter, no spin.  The decision and the arithmetic are
+// handoff_merge's, so the result has the same bits: direct_merge when more than one group exists and few rows carry
+// weight; otherwise the group merges (each group's rows in ascending order against the group's minimum) followed by
+// the merge of the group rows (ascending, against the global minimum), both of which are one round of
+// merge_rows_block here (a group has kGroup <= 32 rows, and there are at most kDirectRows / kGroup <= 16 groups).
+// Only the rho column is read of every row; of the rest, the rows whose own factor and whose group's factor are
+// both non-zero, the ones merge_rows_block would have added.  The group sums stay in registers instead of going
+// through a group row, which changes no bit.
+// The rows' rho come from a compact copy behind the rows (value n * stride + r: 16 cache lines for 256 rows where
+// the column inside the rows touches 256), which the deferred rollout's epilogue stores beside each row's own.
+// l_row: kDirectRows ints of LDS.  Leaves w_eps in sm.weps (and w_eps_out when given) behind a barrier.
+template <int NT, class SM>
+__device__ __forceinline__ void deferred_merge(__amdgpu_buffer_rsrc_t rows, int n, const RowGeo& geo, double inv_lambda,
+                                               SM& sm, int* l_row, double* w_eps_out) {
+    constexpr int P = kDirectRows / 64;
+    // row loads in flight per thread.  64 measured no faster than 32: with many weighted rows (a converged c3 step
+    // that takes this path weights rows in 12 of its 16 groups) the walk below is bound by the lone wave's issue
+    // rate, three uniform LDS reads and two branches per row, not by the round trips
+    constexpr int LB = 32;
+    static_assert(kGroup == 16, "a group is one DPP row of lanes");
+    static_assert(kDirectRows / kGroup <= 16, "the group rows merge in one round in either hand-off form");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int stride = geo.stride, ncol = geo.ncol;   // ncol <= NT: one column per thread
+    double rho_l[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const int r = lane + 64 * j;
+        const double x = ld_prev(rows, r < n ? n * stride + r : kOffRange);
+        rho_l[j] = r < n ? x : INFINITY;
+    }
+    if (n > kGroup && direct_merge<NT, 1, false, true>(rows, n, geo, inv_lambda, sm, nullptr, w_eps_out, 0u, nullptr,
+                                                       nullptr, rho_l))
+        return;
+    // level 1: row lane + 64 j belongs to group (lane >> 4) + 4 j, the 16 lanes of a DPP row in slot j
+    double rho_g[P], m = INFINITY;
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        double v = rho_l[j];
+        v = min_raw_f64(v, dpp_f64<0xB1>(v));
+        v = min_raw_f64(v, dpp_f64<0x4E>(v));
+        v = min_raw_f64(v, dpp_f64<0x141>(v));
+        v = min_raw_f64(v, dpp_f64<0x140>(v));
+        rho_g[j] = v;
+        m = min_raw_f64(m, v);
+    }
+    const double rho = wave_min_f64(m);
+    if (tid < 64) {
+        int base = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const bool in = lane + 64 * j < n;
+            const double s1 = exp((rho_g[j] - rho_l[j]) * inv_lambda);   // the row in its group
+            const double s2 = exp((rho - rho_g[j]) * inv_lambda);        // the group among the groups
+            const bool need = in && s1 >= kMergeFloor && s2 >= kMergeFloor;
+            const unsigned long long bal = __ballot(need);
+            if (need) {
+                const int pos = base + lanes_below(bal);
+                l_row[pos] = lane + 64 * j;
+                sm.rho[pos] = s1;
+                sm.part[pos] = s2;
+            }
+            base += __popcll(bal);
+        }
+        if (lane == 0) sm.nrel = base;
+    }
+    __syncthreads();
+    const int nn = sm.nrel;   // >= 1: the row of the global minimum
+    double acc = 0.0, accg = 0.0;
+    for (int b0 = 0; b0 < nn; b0 += LB) {
+        double v[LB];
+#pragma unroll
+        for (int j = 0; j < LB; ++j) {
+            const int i = b0 + j;
+            v[j] = ld_prev(rows, (i < nn && tid < ncol) ? l_row[i] * stride + 1 + tid : kOffRange);
+        }
+#pragma unroll
+        for (int j = 0; j < LB; ++j) {
+            const int i = b0 + j;
+            if (i < nn) {
+                accg = fma(sm.rho[i], v[j], accg);
+                if (i + 1 == nn || (l_row[i + 1] / kGroup) != (l_row[i] / kGroup)) {   // the group's last row
+                    acc = fma(sm.part[i], accg, acc);
+                    accg = 0.0;
+                }
+            }
+        }
+    }
+    if (tid == 0) {   // column 0 is eta
+        sm.eta = acc;
+        sm.rho_fin = rho;
+    }
+    __syncthreads();
+    if (tid >= 1 && tid < ncol) {
+        const double w = acc / sm.eta;
+        sm.weps[tid - 1] = w;
+        if (w_eps_out) w_eps_out[tid - 1] = w;
+    }
+    __syncthreads();
 }
 
 // Upper median of 10 (rank 5): a 29-comparator sorting network (verified on all

@@ -22,6 +22,9 @@
 //    merges.  One launch covers control.py:81-118.  With MPPI_FLAG_FUSED_UPDATE
 //    the merging workgroup also applies the median filter / update / shift of
 //    control.py:122-149 into the ping-pong step block for the next launch.
+//  * the device-resident loop (MPPI_FLAG_FUSED_UPDATE alone) defers that finish: the DEFER instantiations end at
+//    their rows, and the next launch's prologue merges them and updates the nominal in every workgroup
+//    (deferred_finish; finalize_kernel when something reads the result first).  Same bits, no serial tail.
 //  * torque limits (mppi_config.clamp_mode; the reference's clamp hook _g, control.py:166-172, switched
 //    on): the CLAMP instantiations of the rollout and trajectory kernels clip every sampled control with one
 //    v_med3_f32 per component before the control cost and the dynamics, and the fused update clips the
@@ -329,6 +332,11 @@ __device__ __forceinline__ float cost_pk(f32x2 e, f32x2 f, f32x2 w01, f32x2 w23)
 
 using Scratch = MergeScratch<2 * kMaxT>;
 
+constexpr int kPF = 4;  // noise rows in flight per lane (rollout_kernel)
+
+// Internal launch flag (never in the ABI): the previous launch left its step unfinished (deferred finish below).
+constexpr unsigned kFlagPending = 1u << 31;
+
 // Median filter (scipy.ndimage.median_filter(size=10, mode='reflect'),
 // control.py:319-327, window [t-5, t+4], valid for T >= 5), u += w_eps
 // (control.py:126), shift (control.py:148-149) and the fp32 per-step constants
@@ -364,11 +372,17 @@ __host__ __device__ __forceinline__ double clamp_u(double u, double lo, double h
 // Every thread of the workgroup must call it (it ends with a barrier when
 // host outputs are requested).
 // CLAMP: the kernel was built for torque limits; cl.mode == 2 then clips the updated nominal.
-template <int NT, bool CLAMP>
+// DEFER (the deferred finish, run by every workgroup of the next launch): the fp32 rows (u_t, a_t) also go to s_ua,
+// the LDS rows the horizon loop reads (rows T .. T + kPF - 1 repeat row T - 1); only a workgroup with `store`
+// writes nxt and upd; there are no host outputs (a launch with them finishes its step itself), so no barrier.
+template <int NT, bool CLAMP, bool DEFER = false>
 __device__ void nominal_update_block(DevStep* nxt, const KConst& c, Scratch& sm, double u_src, double u_first,
-                                     float* upd, HostOut ho, const ClampK& cl, bool publish = true) {
+                                     float* upd, HostOut ho, const ClampK& cl, bool publish = true,
+                                     float4* s_ua = nullptr, bool store = true) {
     const int tid = threadIdx.x;
     const int T = c.T;
+    if constexpr (!DEFER) store = true;
+    if (!store) upd = nullptr;
     if (tid < ((2 * T + 63) & ~63)) {   // whole waves: the DPP pairs stay complete
         const int t = tid >> 1, d = tid & 1;
         const int src = t + 1 < T ? t + 1 : T - 1;
@@ -388,13 +402,19 @@ __device__ void nominal_update_block(DevStep* nxt, const KConst& c, Scratch& sm,
         if (tid < 2 * T) {
             if (upd && t + 1 < T) upd[2 * (t + 1) + d] = (float)un;
             if (ho.p) ho.p[4 + tid] = un;
-            nxt->u[t][d] = un;
+            if (store) nxt->u[t][d] = un;
             if (d == 0) {
                 const double u0 = un, u1 = other;
                 const double g0 = c.gamma * u0, g1 = c.gamma * u1;
                 const double a0 = g0 * c.sig_inv[0] + g1 * c.sig_inv[2];
                 const double a1 = g0 * c.sig_inv[1] + g1 * c.sig_inv[3];
-                nxt->ua[t] = make_float4((float)u0, (float)u1, (float)a0, (float)a1);
+                const float4 row = make_float4((float)u0, (float)u1, (float)a0, (float)a1);
+                if (store) nxt->ua[t] = row;
+                if constexpr (DEFER) {
+                    s_ua[t] = row;
+                    if (t == T - 1)
+                        for (int p = 0; p < kPF; ++p) s_ua[T + p] = row;
+                }
             }
         }
     }
@@ -406,9 +426,26 @@ __device__ void nominal_update_block(DevStep* nxt, const KConst& c, Scratch& sm,
     }
 }
 
-// ------------------------------------------------------------ rollout kernel
+// The deferred finish of a fused step: what the step's final workgroup does in the launch itself (handoff_merge's
+// final merge, then nominal_update_block), done one launch later from the rows the step left in `rows` (plain
+// 8-byte values, visible since the kernel boundary).  Every workgroup of the next rollout launch runs it for
+// itself and takes the new nominal's fp32 rows straight into s_ua; the workgroup with `store` (one of them, or
+// the one workgroup of finalize_kernel) also writes what the step leaves in global memory: nxt, w_eps_out, upd.
+// st: the nominal the step ran from.  l_row: kDirectRows ints of LDS.  Every thread must call it; it ends behind
+// a barrier for everything but s_ua (the caller's next barrier).
+template <int NT, bool CLAMP>
+__device__ __forceinline__ void deferred_finish(const KConst& c, const double* rows, const DevStep* st, DevStep* nxt,
+                                                double* w_eps_out, float* upd, const ClampK& cl, Scratch& sm,
+                                                int* l_row, float4* s_ua, bool store) {
+    const int tid = threadIdx.x;
+    const double u_cur = nominal_src(st, tid, c.T), u_first = nominal_first(st, tid);
+    const RowGeo geo(2 * c.T);
+    deferred_merge<NT>(rows_rsrc(rows, c.nblocks * (geo.stride + 1) * 8), c.nblocks, geo, c.inv_lambda, sm, l_row,
+                       store ? w_eps_out : nullptr);
+    nominal_update_block<NT, CLAMP, true>(nxt, c, sm, u_cur, u_first, upd, HostOut{nullptr, 0u}, cl, false, s_ua, store);
+}
 
-constexpr int kPF = 4;  // noise rows in flight per lane
+// ------------------------------------------------------------ rollout kernel
 
 // POLL: the partial rows travel as polled tagged granules; !POLL: behind arrival counters (handoff_merge in
 // mppi_device.h, which both rollout kernels end with).
@@ -418,7 +455,14 @@ constexpr int kPF = 4;  // noise rows in flight per lane
 // colliding states times ob.w joins S after the terminal cost.  Every lane of a sample tests every disc, so S
 // does not depend on LPS.  Instantiated with CLAMP only: without torque limits the limits are -+inf, which the
 // median passes v through untouched.
-template <int LPS, int NT, bool POLL, bool CLAMP, bool OBST>
+// DEFER (the deferred form of a fused step in the device-resident loop; counter-form rows, so with !POLL only): the
+// launch ends once every workgroup has stored its row {rho_b, eta_b, N_b} into `slab`; it has no hand-off, no
+// merge and no update of its own.  Instead, when flags carries kFlagPending, its prologue finishes the PREVIOUS
+// launch's step (deferred_finish) from that launch's rows, which arrive in `gslab`: st is then the nominal that
+// step ran from, and this launch rolls out from the updated one, which every workgroup computes for itself into
+// s_ua while workgroup 0 also stores it to nxt (with w_eps_out and upd) for the launch after this one.  The other
+// instantiations carry no trace of it.
+template <int LPS, int NT, bool POLL, bool CLAMP, bool OBST, bool DEFER = false>
 __global__ __launch_bounds__(NT) void rollout_kernel(
     const KConst c, const StepStatic ss, const DevStep* __restrict__ st, const float2* __restrict__ noise,
     double* __restrict__ S_out, double* __restrict__ slab, double* __restrict__ gslab,
@@ -427,6 +471,8 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     float* __restrict__ upd, const HostOut ho, unsigned long long* __restrict__ dbg, const ClampK cl,
     const ObstK ob) {
     static_assert(CLAMP || !OBST, "the OBST kernels are built with CLAMP only");
+    static_assert(!DEFER || !POLL, "the deferred form leaves plain rows");
+    static_assert(!DEFER || NT >= kDirectRows, "s_k holds the deferred merge's row list");
     __shared__ float4 s_win[kSlots];
     __shared__ float4 s_ua[kMaxT + kPF];   // per-step constants (u_t, a_t); rows >= T repeat row T - 1
     __shared__ double s_redd[NT / 64];
@@ -457,8 +503,15 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     // this launch's granule tag (device epoch + 1), fetched now so its latency is hidden
     const unsigned tag_v = POLL ? __hip_atomic_load(epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u : 0u;
     // nominal element for the fused update, fetched now so its latency is hidden
-    const double u_cur = (flags & MPPI_FLAG_FUSED_UPDATE) ? nominal_src(st, tid, T) : 0.0;
-    const double u_first = (flags & MPPI_FLAG_FUSED_UPDATE) ? nominal_first(st, tid) : 0.0;
+    const double u_cur = (!DEFER && (flags & MPPI_FLAG_FUSED_UPDATE)) ? nominal_src(st, tid, T) : 0.0;
+    const double u_first = (!DEFER && (flags & MPPI_FLAG_FUSED_UPDATE)) ? nominal_first(st, tid) : 0.0;
+    bool pending = false;
+    if constexpr (DEFER) {
+        // the previous launch's step, finished here behind the noise rows already in flight (wave-uniform branch)
+        pending = (flags & kFlagPending) != 0;
+        if (pending) deferred_finish<NT, CLAMP>(c, gslab, st, nxt, w_eps_out, upd, cl, sm, s_k, s_ua, blockIdx.x == 0);
+        STAMP(10, NOW());
+    }
     // window row for the LDS copy: loaded unconditionally (a load inside the
     // tid < kSlots branch would be waited for right there), stored before the barrier
     const float4 wrow = ss.win[tid & (kSlots - 1)];
@@ -478,7 +531,8 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     bool hit_last = false; // ... the newest state among them
     // the per-step constants go to LDS: the ring reads them there, so no scalar
     // load shares lgkmcnt with the deferred row lookup below
-    for (int i = tid; i < T + kPF; i += NT) s_ua[i] = st->ua[i < T ? i : T - 1];
+    if (!pending)
+        for (int i = tid; i < T + kPF; i += NT) s_ua[i] = st->ua[i < T ? i : T - 1];
     if (tid < kSlots) s_win[tid] = wrow;
     __syncthreads();
     float4 uring[kPF];  // per-step constants (u_t, a_t), uniform
@@ -631,7 +685,8 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     const int nrows = c.nblocks;
     const int ngroups = (nrows + kGroup - 1) / kGroup;
     constexpr int kValBytes = POLL ? 16 : 8;
-    const __amdgpu_buffer_rsrc_t slab_r = rows_rsrc(slab, nrows * stride * kValBytes);
+    // (DEFER: the compact copy of the rho column sits behind the rows)
+    const __amdgpu_buffer_rsrc_t slab_r = rows_rsrc(slab, nrows * (stride + (DEFER ? 1 : 0)) * kValBytes);
     const __amdgpu_buffer_rsrc_t gslab_r = rows_rsrc(gslab, ngroups * stride * kValBytes);
     const unsigned tag = __builtin_amdgcn_readfirstlane(tag_v);
     auto publish = [&](int idx, double v) {
@@ -640,6 +695,8 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     };
     const double rho_b = block_min_f64<NT>(owner ? S : INFINITY, sm);
     if (tid == 0) publish(blockIdx.x * stride, rho_b);   // the merger's first need, out at once
+    if constexpr (DEFER)
+        if (tid == 0) publish(nrows * stride + blockIdx.x, rho_b);   // the compact column deferred_merge reads
     // the epilogue's stages: mppi_device.h, "the rollout epilogue"
     const LaneWeight lw = block_weigh(owner, S, rho_b, c.inv_lambda, lane, wave, s_cnt, s_redd);
     __syncthreads();
@@ -699,6 +756,7 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     }
     STAMP(2, NOW());
     STAMP(5, (unsigned long long)nl);
+    if constexpr (DEFER) return;   // the next launch (or finalize_kernel) takes the rows from here
     if (!handoff_merge<NT, 1, POLL>(slab_r, gslab_r, nrows, geo, c.inv_lambda, sm, counters, c.acquire != 0, &s_flag,
                                     partial_out, w_eps_out, tag, epoch, tmo, dbg, dbg))
         return;
@@ -732,6 +790,17 @@ __global__ __launch_bounds__(NT) void merge_kernel(const KConst c, const double*
     merge_rows_block<NT, 1, true, false>(r, 0, n, RowGeo(2 * c.T), c.inv_lambda, sm, nullptr, 0, nullptr, w_eps_out,
                                          0u, nullptr);
     if (flags & MPPI_FLAG_FUSED_UPDATE) nominal_update_block<NT, CLAMP>(nxt, c, sm, u_cur, u_first, upd, ho, cl);
+}
+
+// A pending deferred step finished on its own (one workgroup), when something needs its result before the next
+// rollout launch: deferred_finish as that launch's workgroup 0 runs it.
+template <int NT, bool CLAMP>
+__global__ __launch_bounds__(NT) void finalize_kernel(const KConst c, const double* rows, const DevStep* cur,
+                                                      DevStep* nxt, double* w_eps_out, float* upd, const ClampK cl) {
+    __shared__ Scratch sm;
+    __shared__ int s_row[kDirectRows];
+    __shared__ float4 s_ua[kMaxT + kPF];
+    deferred_finish<NT, CLAMP>(c, rows, cur, nxt, w_eps_out, upd, cl, sm, s_row, s_ua, true);
 }
 
 // Trajectory re-roll (control.py:129-145): control(t) = base[(t-1) mod T] (+ eps).
@@ -911,6 +980,14 @@ struct mppi_ctx {
     StepStatic stat{};          // x0 + window of the next launch (a kernel argument)
     mppi_host::DevBuf<DevStep> d_step;      // [2] ping-pong nominal
     int cur = 0;
+    // Deferred finish of the device-resident loop (launch_rollout): two slabs of plain rows, written in turn, so a
+    // launch reads the previous launch's rows while it writes its own.  `pending`: the last launch left its step
+    // unfinished in slab `drow`; d_step[cur] is still the nominal that step ran from, and d_weps, d_upd and
+    // d_step[cur ^ 1] get its result from the next deferred launch or from finalize_pending, whichever comes first.
+    // [2] slabs of [nblocks][2 + 2T] rows and [nblocks] rho again; none when the grid has more than kDirectRows rows
+    mppi_host::DevBuf<double> d_drows;
+    int drow = 0;
+    bool pending = false;
     mppi_host::PinnedBuf<DevStep> h_step;   // pinned staging of an uploaded nominal
     mppi_host::Event staged;
     bool stage_pending = false;     // a staging copy may still be reading h_step
@@ -964,6 +1041,38 @@ void with_rollout(const mppi_ctx* c, bool poll, F&& f) {
             });
         });
     });
+}
+
+// Is the context's stream being captured into a graph?  (The null stream never is.)
+bool capturing(const mppi_ctx* c) {
+    if (!c->stream) return false;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// Finish a pending deferred step now (one workgroup): called before anything reads or replaces what a fused
+// step leaves (the nominal, w_eps, the unshifted update) other than the next deferred launch, which finishes it
+// itself.  A graph replay cannot track `pending`, so a capture must not begin between a deferred launch and this.
+int finalize_pending(mppi_ctx* c) {
+    if (!c->pending) return MPPI_OK;
+    if (capturing(c))
+        return fail(MPPI_E_ARG, "a deferred fused step is pending on a capturing stream: call mppi_sync before the capture");
+    const size_t slab = (size_t)c->nblocks * (3 + 2 * c->cfg.T);
+    // the rollout kernels' block size: direct_merge's row grouping, and so its bits, depend on it
+    const bool big = c->nt == 512, cl = c->ck.mode != 0;
+    auto* f = big ? (cl ? finalize_kernel<512, true> : finalize_kernel<512, false>)
+                  : (cl ? finalize_kernel<256, true> : finalize_kernel<256, false>);
+    hipLaunchKernelGGL(f, dim3(1), dim3(c->nt), 0, c->stream, c->kc, c->d_drows + c->drow * slab,
+                       c->d_step + c->cur, c->d_step + (c->cur ^ 1), c->d_weps, reinterpret_cast<float*>(c->d_upd.h),
+                       c->ck);
+    if (int rc = launch_check("finalize_kernel")) return rc;
+    c->pending = false;
+    c->cur ^= 1;
+    return MPPI_OK;
 }
 
 // After a launch (rc: its launch_check): a fused update made the other ping-pong block current.  True if so.
@@ -1023,6 +1132,8 @@ int alloc(mppi_ctx* c) {
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + 2 * c->cfg.T, 0)) return rc;
     c->kc.acquire = c->hand.acquire;
     if (int rc = c->d_step.alloc_zeroed(2)) return rc;
+    if (c->nblocks <= kDirectRows)
+        if (int rc = c->d_drows.alloc_zeroed(2 * (size_t)c->nblocks * (3 + 2 * c->cfg.T))) return rc;
     if (int rc = c->d_weps.alloc_zeroed(2 * kMaxT)) return rc;
     if (int rc = c->d_base.alloc(kMaxT)) return rc;
     if (int rc = c->d_upd.alloc(kMaxT)) return rc;
@@ -1124,6 +1235,7 @@ int mppi_ctx_create(const mppi_config* cfg, int device, void* stream, mppi_ctx**
 
 void mppi_ctx_destroy(mppi_ctx* c) {
     if (!c) return;
+    (void)finalize_pending(c);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipDeviceSynchronize();
     delete c;
@@ -1131,6 +1243,8 @@ void mppi_ctx_destroy(mppi_ctx* c) {
 
 int mppi_set_stream(mppi_ctx* c, void* stream) {
     if (!c) return fail(MPPI_E_ARG, "null context");
+    if (c->stream != (hipStream_t)stream)
+        if (int rc = finalize_pending(c)) return rc;   // on the stream its rows were written on
     c->stream = (hipStream_t)stream;
     return MPPI_OK;
 }
@@ -1159,7 +1273,8 @@ int stage_inputs(mppi_ctx* c, const double* x0, const double* window, int W, con
     StepStatic& h = c->stat;
     mppi_host::stage_window(window, W, h.win, h.key, &h.ctr);
     h.x0 = make_float4((float)x0[0], (float)x0[1], (float)x0[2], (float)x0[3]);
-    if (!u) return MPPI_OK;
+    if (!u) return MPPI_OK;   // a pending step stays pending: x0 and the window reach the next launch only
+    if (int rc = finalize_pending(c)) return rc;   // its result lands first, then u replaces the nominal
     const int T = c->cfg.T;
     if (skip_same && c->nominal_published && !memcmp(u, c->h_dout + 4, 2 * (size_t)T * sizeof(double)))
         return MPPI_OK;
@@ -1283,9 +1398,34 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
         if (partial_dev) return fail(MPPI_E_ARG, "MPPI_FLAG_EXCHANGE merges on device: no partial_out");
         partial_dev = c->ex.d_xrow;
     }
+    const float2* nz = reinterpret_cast<const float2*>(noise_dev);
+    // The deferred form (rollout_kernel<..., DEFER>): a fused step whose result nothing takes from the launch itself
+    // ends at its rows, and the next launch finishes it.  Not into a graph (a replay cannot track `pending`).
+    if (flags == MPPI_FLAG_FUSED_UPDATE && !partial_dev && c->d_drows && !capturing(c)) {
+        const size_t slab = (size_t)c->nblocks * (3 + 2 * c->cfg.T);
+        double* prev = c->d_drows + c->drow * slab;
+        double* mine = c->d_drows + (c->drow ^ 1) * slab;
+        const unsigned fl = flags | (c->pending ? kFlagPending : 0u);
+        with_rollout(c, false, [&](auto lps, auto nt, auto p, auto cl, auto ob) {
+            hipLaunchKernelGGL((rollout_kernel<lps, nt, false, cl, ob, true>), dim3(c->nblocks), dim3(nt), 0, c->stream,
+                               c->kc, c->stat, c->d_step + c->cur, nz, S_dev, mine, prev, nullptr, nullptr, c->d_weps,
+                               c->d_step + (c->cur ^ 1), fl, c->ex.xd, nullptr, nullptr,
+                               reinterpret_cast<float*>(c->d_upd.h), HostOut{nullptr, 0u}, c->d_dbg, c->ck, c->ok);
+        });
+        const int rc = launch_check("rollout_kernel");
+        if (rc != MPPI_OK) return rc;
+        if (c->pending) c->cur ^= 1;   // this launch finished the step before it
+        c->drow ^= 1;
+        c->pending = true;
+        c->upd_valid = true;
+        c->nominal_published = false;
+        c->x_flipped = false;
+        return rc;
+    }
+    if (int rc = finalize_pending(c)) return rc;
+    flags &= ~MPPI_FLAG_INLINE_MERGE;
     const DevStep* cur = c->d_step + c->cur;
     DevStep* nxt = c->d_step + (c->cur ^ 1);
-    const float2* nz = reinterpret_cast<const float2*>(noise_dev);
     with_rollout(c, c->hand.poll, [&](auto lps, auto nt, auto p, auto cl, auto ob) {
         hipLaunchKernelGGL((rollout_kernel<lps, nt, p, cl, ob>), dim3(c->nblocks), dim3(nt), 0, c->stream, c->kc, c->stat, cur,
                            nz, S_dev, c->hand.d_slab, c->hand.d_gslab, c->hand.d_counter, partial_dev, c->d_weps, nxt,
@@ -1313,6 +1453,7 @@ int mppi_exchange_attach(mppi_ctx* c, int rank, int world, const void* handles) 
 
 int mppi_merge_partials(mppi_ctx* c, const double* partials_dev, int n, unsigned flags) {
     if (!c || !partials_dev || n < 1) return fail(MPPI_E_ARG, "bad argument");
+    if (int rc = finalize_pending(c)) return rc;
     if ((flags & MPPI_FLAG_FUSED_UPDATE) && c->cfg.T < 5)
         return fail(MPPI_E_ARG, "device median filter needs T >= 5 (use the host update)");
     if ((flags & MPPI_FLAG_HOST_OUT) && !(flags & MPPI_FLAG_FUSED_UPDATE))
@@ -1333,6 +1474,7 @@ int mppi_merge_partials(mppi_ctx* c, const double* partials_dev, int n, unsigned
 
 int mppi_get_weighted_noise(mppi_ctx* c, double* w_eps_host) {
     if (!c || !w_eps_host) return fail(MPPI_E_ARG, "null argument");
+    if (int rc = finalize_pending(c)) return rc;
     const size_t bytes = 2 * (size_t)c->cfg.T * sizeof(double);
     HIP_TRY(hipMemcpyAsync(c->h_buf, c->d_weps, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1342,6 +1484,7 @@ int mppi_get_weighted_noise(mppi_ctx* c, double* w_eps_host) {
 
 int mppi_get_nominal(mppi_ctx* c, double* u_host) {
     if (!c || !u_host) return fail(MPPI_E_ARG, "null argument");
+    if (int rc = finalize_pending(c)) return rc;
     const size_t bytes = 2 * (size_t)c->cfg.T * sizeof(double);
     HIP_TRY(hipMemcpyAsync(c->h_buf, (const char*)(c->d_step + c->cur) + offsetof(DevStep, u), bytes,
                            hipMemcpyDeviceToHost, c->stream));
@@ -1352,6 +1495,7 @@ int mppi_get_nominal(mppi_ctx* c, double* u_host) {
 
 int mppi_rollout_traj(mppi_ctx* c, const double* base_u, const float* noise_dev, int K, float* out_dev) {
     if (!c || !out_dev || K < 1 || K > c->cfg.K_local) return fail(MPPI_E_ARG, "bad argument");
+    if (int rc = finalize_pending(c)) return rc;
     const DevStep* cur = c->d_step + c->cur;
     const float2* base;
     int bstride = 1;
@@ -1374,6 +1518,7 @@ int mppi_rollout_traj(mppi_ctx* c, const double* base_u, const float* noise_dev,
 
 int mppi_optimal_traj(mppi_ctx* c, float* out_dev) {
     if (!c || !out_dev) return fail(MPPI_E_ARG, "null argument");
+    if (int rc = finalize_pending(c)) return rc;
     if (!c->upd_valid) return fail(MPPI_E_ARG, "mppi_optimal_traj needs a preceding MPPI_FLAG_FUSED_UPDATE launch");
     launch_traj(c, 1, c->d_upd, 1, nullptr, 1, reinterpret_cast<float4*>(out_dev));
     return launch_check("traj_kernel");
@@ -1381,6 +1526,7 @@ int mppi_optimal_traj(mppi_ctx* c, float* out_dev) {
 
 int mppi_get_step_outputs(mppi_ctx* c, double* u_host, const float* traj_dev, float* traj_host) {
     if (!c || !u_host || (traj_dev && !traj_host)) return fail(MPPI_E_ARG, "bad argument");
+    if (int rc = finalize_pending(c)) return rc;
     const int T = c->cfg.T;
     const size_t ub = 2 * (size_t)T * sizeof(double), tb = 4 * (size_t)T * sizeof(float);
     float* h_traj = reinterpret_cast<float*>(c->h_out + 2 * kMaxT);
@@ -1572,6 +1718,7 @@ int mppi_debug_set_buffer(mppi_ctx* c, void* dbg_dev) {
 
 int mppi_debug_nearest(mppi_ctx* c, const float* noise_dev, int K, int* slot_dev, float* pos_dev) {
     if (!c || !noise_dev || !slot_dev || !pos_dev || K < 1 || K > c->cfg.K_local) return fail(MPPI_E_ARG, "bad argument");
+    if (int rc = finalize_pending(c)) return rc;
     hipLaunchKernelGGL(nearest_debug_kernel, dim3((K + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, c->kc,
                        c->stat, c->d_step + c->cur, reinterpret_cast<const float2*>(noise_dev), K, slot_dev,
                        reinterpret_cast<float2*>(pos_dev), c->ck);
@@ -1601,6 +1748,7 @@ int mppi_set_obstacles(mppi_ctx* c, int n, const double* discs, double cost) {
 
 int mppi_debug_obstacle_hits(mppi_ctx* c, const float* noise_dev, int K, unsigned* mask_dev, float* dir_dev) {
     if (!c || !noise_dev || !mask_dev || !dir_dev || K < 1 || K > c->cfg.K_local) return fail(MPPI_E_ARG, "bad argument");
+    if (int rc = finalize_pending(c)) return rc;
     hipLaunchKernelGGL(obstacle_debug_kernel, dim3((K + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, c->kc,
                        c->stat, c->d_step + c->cur, reinterpret_cast<const float2*>(noise_dev), K, mask_dev,
                        reinterpret_cast<float4*>(dir_dev), c->ck, c->ok);
@@ -1615,8 +1763,15 @@ int mppi_debug_dropin_times(const mppi_ctx* c, double* us_out) {
 
 int mppi_sync(mppi_ctx* c) {
     if (!c) return fail(MPPI_E_ARG, "null context");
+    if (int rc = finalize_pending(c)) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return check_timeout(c);
+}
+
+int mppi_debug_pending(const mppi_ctx* c, int* pending) {
+    if (!c || !pending) return fail(MPPI_E_ARG, "null argument");
+    *pending = c->pending ? 1 : 0;
+    return MPPI_OK;
 }
 
 int mppi_ctx_handoff(const mppi_ctx* c, int* poll) {

@@ -111,9 +111,10 @@ class _Engine:
             return
         s = torch.cuda.current_stream(self.device)
         if s.cuda_stream != self.stream.cuda_stream:
+            # the context first: it may queue work of its own on the old stream (a pending deferred step's finish)
+            N.check(self._c_set_stream(self._ctx, C.c_void_p(s.cuda_stream)), self._prefix + "set_stream")
             s.wait_stream(self.stream)
             self.stream = s
-            N.check(self._c_set_stream(self._ctx, C.c_void_p(s.cuda_stream)), self._prefix + "set_stream")
 
     # -- buffers ------------------------------------------------------------
     def new_noise(self) -> torch.Tensor:
@@ -198,9 +199,14 @@ class _Engine:
 
     def rollout(self, noise: torch.Tensor, S_out: torch.Tensor | None = None,
                 partial_out: torch.Tensor | None = None, fused_update: bool = False, exchange: bool = False,
-                host_out: bool = False) -> None:
+                host_out: bool = False, merge: str = "auto") -> None:
         """control.py:81-118 for this shard; `exchange`: also exchange and merge the ranks' rows in the launch;
-        `host_out` (with fused_update): publish the result to host-mapped memory for wait_outputs()."""
+        `host_out` (with fused_update): publish the result to host-mapped memory for wait_outputs().
+        `merge` (the arm, fused_update alone): "auto" lets the context defer the step's merge and update to the
+        next launch's prologue (the device-resident loop; the same bits), "inline" finishes it in this launch
+        (MPPI_FLAG_INLINE_MERGE).  The chain engine has no deferred form: there the argument has no effect."""
+        if merge not in ("auto", "inline"):
+            raise ValueError('merge must be "auto" or "inline"')
         self._sync_stream()
         self._check_noise(noise)
         if S_out is not None:
@@ -212,7 +218,8 @@ class _Engine:
                                 C.c_void_p(partial_out.data_ptr()) if partial_out is not None else None,
                                 (N.MPPI_FLAG_FUSED_UPDATE if fused_update else 0)
                                 | (N.MPPI_FLAG_EXCHANGE if exchange else 0)
-                                | (N.MPPI_FLAG_HOST_OUT if host_out else 0)),
+                                | (N.MPPI_FLAG_HOST_OUT if host_out else 0)
+                                | (N.MPPI_FLAG_INLINE_MERGE if merge == "inline" and self._prefix == "mppi_" else 0)),
                 self._prefix + "rollout")
 
     def merge(self, partials: torch.Tensor, n: int, fused_update: bool = False, flags: int = 0) -> None:
@@ -338,6 +345,13 @@ class RolloutEngine(_Engine):
         # in-launch hand-off of the workgroup partials: "poll" (tagged granules) or "counter"
         self.handoff = "poll" if poll.value else "counter"
         self.obstacles, self.obstacle_cost = np.zeros((0, 3)), 0.0   # what set_obstacles last gave the context
+
+    def pending(self) -> bool:
+        """Diagnostics: the last fused launch took the deferred form and its step is not finished yet
+        (mppi_debug_pending)."""
+        p = C.c_int()
+        N.check(self._lib.mppi_debug_pending(self._ctx, C.byref(p)), "mppi_debug_pending")
+        return bool(p.value)
 
     def merge(self, partials: torch.Tensor, n: int, fused_update: bool = False, host_out: bool = False) -> None:
         super().merge(partials, n, fused_update, N.MPPI_FLAG_HOST_OUT if host_out else 0)   # host_out: the arm only

@@ -61,18 +61,29 @@ for i in range(steps):
     cu = (d[:, 9] & 0xF) * 1000 + ((hw >> 13) & 7) * 100 + ((hw >> 12) & 1) * 16 + ((hw >> 8) & 0xF)
     _, per_cu = np.unique(cu, return_counts=True)
     occ = f"blocks/CU {np.bincount(per_cu).tolist()}"
-    print(f"step {i:2d}: {occ} | event {s0.elapsed_time(s1)*1e3:6.1f} | rollout med {np.median(roll):5.1f} max {roll.max():5.1f} "
-          f"| epi med {np.median(epi):4.1f} max {epi.max():4.1f} | last epi end {us(d[:, 2].max()):5.1f} | final wg: "
-          f"grp-arrive {us(d[last, 3]):5.1f} grp-merge {us(d[last, 10]):5.1f} fin-arrive {us(d[last, 4]):5.1f} "
-          f"fin-merge {us(d[last, 11]):5.1f} update {us(d[last, 7]):5.1f} | nl med {np.median(d[:, 5]):.0f} max {d[:, 5].max()} "
-          f"| rows {d[last, 6]}")
-    if d[last, 13] and d[last, 14] and d[last, 13] > d[last, 3]:
+    # the deferred form: no merge in the launch (slot 7 never written), the previous step's finish in the prologue
+    # (slot 10 is its end); the merger's slots then hold nothing of this launch
+    deferred = not d[:, 7].any() and d[:, 10].any()
+    if deferred:
+        fin = (d[:, 10] - d[:, 0]) / 100.0
+        print(f"step {i:2d}: {occ} | event {s0.elapsed_time(s1)*1e3:6.1f} | rollout med {np.median(roll):5.1f} max {roll.max():5.1f} "
+              f"| epi med {np.median(epi):4.1f} max {epi.max():4.1f} | last rows out {us(d[:, 2].max()):5.1f} "
+              f"| nl med {np.median(d[:, 5]):.0f} max {d[:, 5].max()}")
+        print(f"         deferred form: previous step finished {np.median(fin):.2f} us (max {fin.max():.2f}) after each "
+              f"workgroup's start")
+    else:
+        print(f"step {i:2d}: {occ} | event {s0.elapsed_time(s1)*1e3:6.1f} | rollout med {np.median(roll):5.1f} max {roll.max():5.1f} "
+              f"| epi med {np.median(epi):4.1f} max {epi.max():4.1f} | last epi end {us(d[:, 2].max()):5.1f} | final wg: "
+              f"grp-arrive {us(d[last, 3]):5.1f} grp-merge {us(d[last, 10]):5.1f} fin-arrive {us(d[last, 4]):5.1f} "
+              f"fin-merge {us(d[last, 11]):5.1f} update {us(d[last, 7]):5.1f} | nl med {np.median(d[:, 5]):.0f} max {d[:, 5].max()} "
+              f"| rows {d[last, 6]}")
+    if not deferred and d[last, 13] and d[last, 14] and d[last, 13] > d[last, 3]:
         print(f"         merger: rho seen {us(d[last, 13]):5.1f}, weighted rows loaded {us(d[last, 14]):5.1f}")
-    if d[:, 15].any():
+    if not deferred and d[:, 15].any():
         print(f"         last rho published {us(d[:, 15].max()):5.1f} (loop end of that wg {us(d[np.argmax(d[:, 15]), 1]):5.1f})"
               f" -> final merge done {us(d[last, 11]):5.1f}")
     gm = d[:, 10][d[:, 10] > 0]
-    if len(gm) and (np.arange(len(d)) != last).any():
+    if not deferred and len(gm) and (np.arange(len(d)) != last).any():
         others = [b for b in range(len(d)) if b != last and d[b, 10] > 0]
         if others:
             print(f"         level-1 group mergers: {len(others)}, last done {us(max(d[b, 10] for b in others)):5.1f} "
