@@ -13,7 +13,7 @@
 //    the window search of the 2-link engine -> stage + control cost.  Noise is
 //    [T][K][N] fp32 (like the 2-link engine's [T][K][2]): a sample's N values of
 //    a step contiguous, so a weighted sample's noise is T cache lines.  Same epilogue,
-//    in-launch merges and fused update as the 2-link engine (mppi_device.h),
+//    in-launch merges and fused update as the 2-link engine (mppi_device.h, mppi_merge.h),
 //    with T*N columns per partial row (MAXCH = 4 column chunks).
 //  * chain_traj_kernel<N, NOISE>, chain_philox_kernel: trajectory re-roll and
 //    counter-based Gaussian noise with an n x n Cholesky factor.
@@ -86,9 +86,7 @@ struct ChainClampK {
     float v_lo[kCMax], v_hi[kCMax];
     int mode;   // mppi_chain_config.clamp_mode
 };
-// np.clip in fp64: an operand comes back untouched (a NaN u too)
-__host__ __device__ __forceinline__ double clamp_u(double u, double lo, double hi) { return u < lo ? lo : (u > hi ? hi : u); }
-// the fp32 clip: v_med3_f32 (lo <= hi is guaranteed by mppi_chain_ctx_create), no canonicalising v_max / v_min
+// the fp32 clip (the fp64 one is clamp_u, mppi_device.h): v_med3_f32 (lo <= hi is guaranteed by mppi_chain_ctx_create), no canonicalising v_max / v_min
 __device__ __forceinline__ float clamp_v(float v, float lo, float hi) { return __builtin_amdgcn_fmed3f(v, lo, hi); }
 // entry d (a lane value) of a by-value table, as selects over its N compile-time entries (no dynamic index
 // into the kernel argument)
@@ -955,7 +953,7 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
     return q_sum_f64(S);
 }
 
-// POLL / counter: the hand-off form of the partial rows (handoff_merge in mppi_device.h, shared with rollout_kernel).
+// POLL / counter: the hand-off form of the partial rows (handoff_merge in mppi_merge.h, shared with rollout_kernel).
 // SLOTS (debug instances, mppi_chain_debug_slots): dbg receives the window slot
 // each sample picked at each step, int32 [k][t].
 // CLAMP: the sampled controls are clipped to the torque limits cl (clamp_mode != 0) and, with cl.mode == 2, so
@@ -1225,8 +1223,8 @@ __global__ __launch_bounds__(kCT) void chain_merge_kernel(const ChainConst c, co
     chain_nominal_prefetch<N>(cur, T, flags & MPPI_FLAG_FUSED_UPDATE, u_cur);
     const RowGeo geo(T * N);
     const __amdgpu_buffer_rsrc_t r = rows_rsrc(parts, n * geo.stride * 8);
-    merge_rows_block<kCT, kCMaxCh, true, false>(r, 0, n, geo, c.inv_lambda, sm, nullptr, 0, nullptr, w_eps_out, 0u,
-                                                nullptr);
+    merge_rows_block<kCT, kCMaxCh, true, RowsVia::Wt>(r, 0, n, geo, c.inv_lambda, sm, nullptr, 0, nullptr, w_eps_out,
+                                                      0u, nullptr);
     if (tid == 0 && w_eps_out) w_eps_out[T * N] = sm.eta;
     if (flags & MPPI_FLAG_FUSED_UPDATE) chain_update_block<N, CLAMP>(nxt, c, sm, u_cur, cl);
 }

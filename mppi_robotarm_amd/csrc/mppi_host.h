@@ -19,7 +19,7 @@
 #include <string>
 #include <type_traits>
 
-#include "mppi_device.h"  // XDesc, kSlots, kPadKey, kGroup, kMaxWorld, kTmo*
+#include "mppi_device.h"  // (with mppi_merge.h) XDesc, kSlots, kPadKey, kGroup, kMaxWorld, kTmo*
 #include "mppi_rocm.h"
 
 namespace mppi_host {
@@ -218,7 +218,7 @@ inline void stage_window(const double* window, int W, float4* win, float4* key, 
 // ------------------------------------------------- in-launch hand-off
 
 // Reads and clears the two host-mapped time-out words (tmo[0]: a local hand-off gave up, kTmoLocal; tmo[1]:
-// the exchange's verdict bits, mppi_device.h) and records the verdict's message: MPPI_OK when neither is
+// the exchange's verdict bits, mppi_merge.h) and records the verdict's message: MPPI_OK when neither is
 // set.  *bits gets the verdict, for the caller's own roll-back: kTmoExchange alone means every rank of the
 // step reports it and none applied the update, so the step can run again from the nominal before the launch.
 inline int take_timeout(unsigned* h_tmo, unsigned* bits) {

@@ -363,9 +363,6 @@ struct HostOut {
     unsigned seq;
 };
 
-// np.clip of one fp64 control (lo <= hi; a NaN passes through, as everywhere outside the contract)
-__host__ __device__ __forceinline__ double clamp_u(double u, double lo, double hi) { return u < lo ? lo : (u > hi ? hi : u); }
-
 // upd (nullable): the updated, not yet shifted controls u_new[t] in fp32, the
 // base of the optimal trajectory (control.py:129-134, mppi_optimal_traj):
 // u_new[t + 1] is this thread's shifted element, u_new[0] one more median.
@@ -448,7 +445,7 @@ __device__ __forceinline__ void deferred_finish(const KConst& c, const double* r
 // ------------------------------------------------------------ rollout kernel
 
 // POLL: the partial rows travel as polled tagged granules; !POLL: behind arrival counters (handoff_merge in
-// mppi_device.h, which both rollout kernels end with).
+// mppi_merge.h, which both rollout kernels end with).
 // CLAMP: the sampled controls are clipped to the torque limits (clamp_mode != 0); the CLAMP = false
 // instantiations carry no trace of it.
 // OBST: every step's new state, and the final state once more, is tested against the discs of ob; the count of
@@ -787,8 +784,8 @@ __global__ __launch_bounds__(NT) void merge_kernel(const KConst c, const double*
     const double u_cur = (flags & MPPI_FLAG_FUSED_UPDATE) ? nominal_src(cur, tid, c.T) : 0.0;
     const double u_first = (flags & MPPI_FLAG_FUSED_UPDATE) ? nominal_first(cur, tid) : 0.0;
     const __amdgpu_buffer_rsrc_t r = rows_rsrc(parts, n * (2 + 2 * c.T) * 8);
-    merge_rows_block<NT, 1, true, false>(r, 0, n, RowGeo(2 * c.T), c.inv_lambda, sm, nullptr, 0, nullptr, w_eps_out,
-                                         0u, nullptr);
+    merge_rows_block<NT, 1, true, RowsVia::Wt>(r, 0, n, RowGeo(2 * c.T), c.inv_lambda, sm, nullptr, 0, nullptr,
+                                               w_eps_out, 0u, nullptr);
     if (flags & MPPI_FLAG_FUSED_UPDATE) nominal_update_block<NT, CLAMP>(nxt, c, sm, u_cur, u_first, upd, ho, cl);
 }
 

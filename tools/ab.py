@@ -6,6 +6,7 @@ the builds, so clock and thermal drift hit both alike.
     WORKLOAD=c5: the 7-link chain engine (default K 131072, T 128)
     WORKLOAD=philox: the arm's noise draw (mppi_noise_philox) instead of the rollout
     LPS=n: lanes per sample of every arm build; LPS_LIST=a,b,...: per build (the same .so may repeat)
+    MERGE=inline: the arm's fused launches finish their step in the launch (MPPI_FLAG_INLINE_MERGE)
 
 Prints, per build, the median / min per-launch time (HIP events around each
 batch on the launching stream) and each build's ratio to the first.
@@ -87,9 +88,11 @@ def arm_runs(libs, K, T, lam, stream):
         for i, nz in enumerate(noise):
             assert L.mppi_noise_philox(ctx, 1234, i, C.c_void_p(nz.data_ptr())) == 0
 
+        flags = N.MPPI_FLAG_FUSED_UPDATE | (N.MPPI_FLAG_INLINE_MERGE if os.environ.get("MERGE") == "inline" else 0)
+
         def batch(n, L=L, ctx=ctx, noise=noise):
             for i in range(n):
-                assert L.mppi_rollout(ctx, C.c_void_p(noise[i % len(noise)].data_ptr()), None, None, 1) == 0
+                assert L.mppi_rollout(ctx, C.c_void_p(noise[i % len(noise)].data_ptr()), None, None, flags) == 0
         runs.append((f"{os.path.basename(p)} lps={lp}", batch, lambda L=L, ctx=ctx: L.mppi_ctx_destroy(ctx), []))
     return runs
 
