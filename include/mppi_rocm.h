@@ -512,10 +512,46 @@ int mppi_chain_debug_set_buffer(mppi_chain_ctx *ctx, void *dbg_dev);
  * through a build of the same kernel that also records the window slot every
  * sample picked at every step (the argmin of control.py:205-215 inside _c),
  * slots_dev int32 [K_local][T].  7-link contexts only, and only without torque
- * limits (the recording instances are unclamped: MPPI_E_ARG with clamp_mode > 0).
+ * limits or obstacles (the recording instances have neither: MPPI_E_ARG with
+ * clamp_mode > 0 or with discs set).
  * The parity tests use it to recompute a sample's fp64 cost with the device's own
  * picks. */
 int mppi_chain_debug_slots(mppi_chain_ctx *ctx, const float *noise_dev, double *S_dev, int *slots_dev);
+
+/* Workspace obstacles for the chain: mppi_set_obstacles' collision cost on every
+ * link.  Up to MPPI_MAX_OBSTACLES discs (cx, cy, r), discs[n][3] row-major, and one
+ * cost >= 0.  Link a (0-based, a < chain.n) is the zero-thickness segment from
+ * b_{a-1} to b_a, b_a = sum_{i <= a} fk_i (cos th_i, sin th_i) with b_{-1} the origin,
+ * th_i the absolute angles and fk the cost's link lengths (the end effector of the
+ * stage cost is b_{n-1}); it touches a disc when the distance from the centre to the
+ * segment, the projection clipped to [0, fk_a], is < r (a margin or a link thickness
+ * goes into r).  A state collides when any link touches any disc.  Every step of the
+ * horizon whose new state collides adds `cost` to that sample's S, and the final
+ * state adds it once more: S = S_track + cost * hits, hits in [0, T + 1].  Dynamics,
+ * weights, weighted noise, update, the trajectories, the exploration split and the
+ * torque limits are untouched.  At n = 2 with the arm's constants this is
+ * mppi_set_obstacles' definition.  The test runs in the rollout's own arithmetic on
+ * its own (cos, sin) values: in fp32 for precision 0 (a state within a few 1e-6 m of
+ * a disc's boundary may fall on either side), in fp64 on the fp64 centres and r for
+ * precision 1.
+ *
+ * As mppi_set_obstacles: in effect from the next launch of any kind, the discs a
+ * by-value argument of that launch (a captured graph freezes the discs it was
+ * captured with); n = 0 removes them and the context then launches exactly the
+ * kernels it launched before any were set.  No device call.  MPPI_E_ARG for n
+ * outside 0..MPPI_MAX_OBSTACLES, a NaN or negative r, a non-finite centre, and a NaN,
+ * negative or infinite cost; the discs in effect are then kept. */
+int mppi_chain_set_obstacles(mppi_chain_ctx *ctx, int n, const double *discs, double cost);
+
+/* Tests: the collision test of the first K samples at every step as the context's
+ * rollout evaluates it (the same kernel: its precision, its lanes per sample, its
+ * step and its hit function) on the current step inputs, discs and noise_dev
+ * ([T][K_local][n] fp32).  mask_dev[K][T] (uint64 device): bit 8 j + a set when link
+ * a touches disc j; dir_dev[K][T][2 n] (fp32 device): cos th_a at index a and
+ * sin th_a at index n + a, the values the test was evaluated on (rounded to fp32
+ * for precision 1).  Nothing of the context's step state changes. */
+int mppi_chain_debug_obstacle_hits(mppi_chain_ctx *ctx, const float *noise_dev, int K,
+                                   unsigned long long *mask_dev, float *dir_dev);
 
 /* ------------------------------------------------------------------------
  * The reference's own noise on the device: NumPy's legacy global-RNG stream of

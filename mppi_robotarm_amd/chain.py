@@ -159,6 +159,22 @@ class ChainEngine(_Engine):
                                                  C.c_void_p(slots.data_ptr())), "mppi_chain_debug_slots")
         return slots.cpu().numpy()
 
+    def obstacle_hits(self, noise: torch.Tensor, K: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Tests: the collision test of the first K samples per step as this context's rollout evaluates it
+        (mppi_chain_debug_obstacle_hits: its precision, its lanes per sample, its step and hit functions) ->
+        (mask (K, T) uint64: bit 8 j + a link a touches disc j; dir (K, T, 2 n) fp32: cos th_a at a, sin th_a
+        at n + a, the values the test ran on)."""
+        self._sync_stream()
+        self._check_noise(noise)
+        K = self.K_local if K is None else int(K)
+        mask = torch.zeros((K, self.T), dtype=torch.int64, device=self.device)
+        d = torch.zeros((K, self.T, 2 * self.n), dtype=torch.float32, device=self.device)
+        N.check(self._lib.mppi_chain_debug_obstacle_hits(self._ctx, C.c_void_p(noise.data_ptr()), K,
+                                                         C.c_void_p(mask.data_ptr()), C.c_void_p(d.data_ptr())),
+                "mppi_chain_debug_obstacle_hits")
+        self.synchronize()
+        return mask.cpu().numpy().view(np.uint64), d.cpu().numpy()
+
 
 class ChainMPPIController(MPPIControllerBase):
     """control.py:20-152 for the n-link chain (dim_u = n, dim_x = 2n).
@@ -176,7 +192,14 @@ class ChainMPPIController(MPPIControllerBase):
     reference's clamp hook ``_g`` (control.py:166-172) switched on: the sampled controls are clipped before the
     dynamics and the control cost, the weights still multiply the unclamped noise, and with
     ``visualize_optimal_traj`` the updated nominal is clipped too.  Both engines of ``precision="auto"`` carry
-    them."""
+    them.
+
+    ``obstacles`` / ``obstacle_cost``: up to eight discs ``(cx, cy, r)`` that no link may touch, as on the arm
+    controller: every colliding step of a sample, and its final state once more, adds ``obstacle_cost`` to its
+    cost (mppi_chain_set_obstacles).  Plain attributes, compared by value on every call, so they may be edited in
+    place or rebound between calls; a bad value raises ValueError before anything is drawn or moved.  Every
+    engine a step runs on (``precision="auto"``'s fp64 one, every rank's of a process group) gets them before its
+    launch."""
 
     ETA_TOL = 1e-6   # weight outside the best sample above which precision="auto" takes the fp64 rollout
 
@@ -188,7 +211,8 @@ class ChainMPPIController(MPPIControllerBase):
                  visualize_optimal_traj=True, visualze_sampled_trajs=False, *, chain: ChainParams = ChainParams(),
                  u_init=None, device: int | None = None, verbose: bool = False, noise: str = "numpy", seed: int = 0,
                  process_group=None, exchange: str = "auto", precision: str = "auto",
-                 numpy_noise_on_device: bool = True, u_min=None, u_max=None) -> None:
+                 numpy_noise_on_device: bool = True, u_min=None, u_max=None, obstacles=None,
+                 obstacle_cost: float = 1.0e10) -> None:
         self.chain = chain
         if precision not in ("auto", "f32", "f64"):
             raise ValueError("precision must be 'auto', 'f32' or 'f64'")
@@ -208,6 +232,11 @@ class ChainMPPIController(MPPIControllerBase):
                          exchange=exchange, numpy_noise_on_device=numpy_noise_on_device)
         self.u_min, self.u_max = u_min, u_max   # properties (MPPIControllerBase): torque limits of _g, validated
         self._limits()                          # u_min <= u_max
+        self.obstacles = obstacles              # (n, 3) array-like of discs (cx, cy, r), n <= 8, or None
+        self.obstacle_cost = obstacle_cost      # added to S per colliding step (and once for the final state)
+        self._obst_checked = None               # the last (obstacles bytes, cost) that passed the checks
+        self._okey = None                       # this call's key (_obstacle_key), for _device_step
+        self._obstacle_key()
         self._slots = {}               # rollout precision -> the parked state of its engine (_SLOT fields)
         self._active = None            # the precision whose engine the per-engine fields hold
         self._spread = False           # precision="auto": the last step's weights were spread (next step fp64)
@@ -284,6 +313,7 @@ class ChainMPPIController(MPPIControllerBase):
         return nearest_idx
 
     def calc_control_input(self, observed_x):
+        self._okey = self._obstacle_key()                  # ValueError before anything is drawn or moved
         if self._npre is not None and self.noise_source != "numpy":
             self._settle_predraw()                         # (the NumPy path settles it after its checks)
         u = self.u_prev
@@ -342,6 +372,7 @@ class ChainMPPIController(MPPIControllerBase):
         if key != self._engine_built_for:
             np.linalg.inv(self.Sigma)                      # LinAlgError as control.py:106 (Sigma checked when it changes)
         eng = self._get_engine(key)
+        self._push_obstacles(eng, self._okey)              # this call's discs, before any launch of this engine
         if isinstance(epsilon, DeviceDrawn):               # a device draw, into one engine's buffer
             if epsilon.buf is not self._noise_dev:
                 eng._sync_stream()

@@ -190,35 +190,6 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
             self._xmode = None
         return self._engine
 
-    # ------------------------------------------------------------ obstacles
-    def _obstacle_key(self):
-        """self.obstacles / self.obstacle_cost by value: None without discs, else (the (n, 3) fp64 bytes, the
-        cost), checked (ValueError for a bad shape or value).  Compared on every call, the bound tick's too,
-        so a rebind and an in-place edit are both seen."""
-        if self.obstacles is None:
-            return None
-        try:
-            a = np.array(self.obstacles, dtype=np.float64, ndmin=1)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"obstacles: {e}") from None
-        if a.size == 0:
-            return None
-        try:
-            key = (a.shape, a.tobytes(), float(self.obstacle_cost))
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"obstacle_cost: {e}") from None
-        if key != self._obst_checked:
-            RolloutEngine.check_obstacles(a, self.obstacle_cost)
-            self._obst_checked = key
-        return key
-
-    def _push_obstacles(self, eng: RolloutEngine, key) -> None:
-        """Give the engine this call's discs unless it holds them already (no device call either way)."""
-        have = eng.obstacles
-        have = (have.shape, have.tobytes(), eng.obstacle_cost) if have.shape[0] else None
-        if key != have:
-            eng.set_obstacles(None if key is None else self.obstacles, self.obstacle_cost)
-
     def _multi_rollout(self, eng: RolloutEngine, S_out, fused: bool) -> None:
         """control.py:81-118 over every rank's shard, the rows merged on every rank:
         one launch with the in-launch exchange, or rollout + RCCL all-gather + merge

@@ -19,7 +19,7 @@ import torch
 
 from . import hostrng
 from .distributed import attach_exchange, check_exchange, same_on_all_ranks
-from .engine import HostReadback, NpDeviceStream
+from .engine import HostReadback, NpDeviceStream, _Engine
 
 
 def first_min_index(d: np.ndarray) -> int:
@@ -227,6 +227,36 @@ class MPPIControllerBase:
         if lim is not None:
             np.clip(v, lim[0], lim[1], out=v)
         return v
+
+    # ------------------------------------------------------------ obstacles (both drop-ins)
+    def _obstacle_key(self):
+        """self.obstacles / self.obstacle_cost by value: None without discs, else (the (n, 3) fp64 bytes, the
+        cost), checked (ValueError for a bad shape or value).  Compared on every call, the bound tick's too,
+        so a rebind and an in-place edit are both seen.  A subclass sets the two plain attributes and
+        ``_obst_checked = None`` (the last key that passed the checks)."""
+        if self.obstacles is None:
+            return None
+        try:
+            a = np.array(self.obstacles, dtype=np.float64, ndmin=1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"obstacles: {e}") from None
+        if a.size == 0:
+            return None
+        try:
+            key = (a.shape, a.tobytes(), float(self.obstacle_cost))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"obstacle_cost: {e}") from None
+        if key != self._obst_checked:
+            _Engine.check_obstacles(a, self.obstacle_cost)
+            self._obst_checked = key
+        return key
+
+    def _push_obstacles(self, eng, key) -> None:
+        """Give the engine this call's discs unless it holds them already (no device call either way)."""
+        have = eng.obstacles
+        have = (have.shape, have.tobytes(), eng.obstacle_cost) if have.shape[0] else None
+        if key != have:
+            eng.set_obstacles(None if key is None else self.obstacles, self.obstacle_cost)
 
     # ------------------------------------------------------------ engine
     def _shard(self):

@@ -22,6 +22,10 @@
 //    control (v_med3_f32 in the fp32 forms, fp64 compares in the fp64 one) and, in mode 2, the updated nominal
 //    in fp64.  The limits travel in ChainClampK, the kernels' last argument, which the other instantiations
 //    never read.
+//  * workspace obstacles (mppi_chain_set_obstacles): the OBST instantiations of the rollout kernel, in its three forms,
+//    test every link against up to eight discs after every step and add cost x (colliding states) to S.  The discs
+//    travel in ChainObstK, the last argument after ChainClampK; a context without discs launches the kernels it
+//    launched before.
 //
 // C ABI: include/mppi_rocm.h (mppi_chain_*).
 #include <hip/hip_runtime.h>
@@ -97,6 +101,19 @@ __device__ __forceinline__ T pick(const T (&tab)[kCMax], int d) {
     for (int e = 1; e < N; ++e) r = d == e ? tab[e] : r;
     return r;
 }
+
+// Workspace obstacles (mppi_chain_set_obstacles): up to MPPI_MAX_OBSTACLES discs, the centres and r^2 in fp32 (the
+// fp32 rollouts: ObstR's records, mppi_device.h) and in fp64 (the fp64 rollout), and the cost of one colliding
+// state; an unused entry has r2 = -1, which no squared distance is below.  A per-launch input like x0: the last
+// argument of the rollout kernel, after ChainClampK, read by the OBST instantiations only.
+struct ChainObstK {
+    float cx[MPPI_MAX_OBSTACLES], cy[MPPI_MAX_OBSTACLES], r2[MPPI_MAX_OBSTACLES];
+    double cxd[MPPI_MAX_OBSTACLES], cyd[MPPI_MAX_OBSTACLES], r2d[MPPI_MAX_OBSTACLES];
+    double w;
+    int n;
+};
+// what mppi_chain_debug_obstacle_hits records: bit 8 j + a of a mask is link a against disc j
+using ObstMask = unsigned long long;
 
 using CScratch = MergeScratch<kCMaxVals>;
 
@@ -477,6 +494,88 @@ struct ChainStateD {
     }
 };
 
+// ---- workspace obstacles (mppi_chain_set_obstacles): does a state collide.  Link a is the zero-thickness segment
+// from b_{a-1} to b_a = sum_{i <= a} fk_i (cos th_i, sin th_i) (b_{-1} the origin) in the cost's kinematics, the
+// one effector() sums; it touches a disc when the centre's distance to it, the projection clipped to [0, fk_a], is
+// below r.  The three rollout forms evaluate that on the (cos, sin) their step just produced (no transcendental is
+// added), with the arm's seg_hits (mppi_device.h) in fp32 and the same operations in doubles in fp64; each has a
+// MASK variant for mppi_chain_debug_obstacle_hits that runs the same operations and keeps every comparison
+// (bit 8 j + a: link a against disc j) where the rollout keeps their OR.
+//
+// One lane per sample: the disc pairs outermost and the links walked inside, so only one pair's centres relative
+// to the current link's base are live (4 VGPRs): the base moves along the chain with two v_pk_fma per link, the
+// arm's qX, qY repeated.  NP = 0: a scalar branch per pair in use (o.n is wave-uniform), the pairs unrolled; NP < 0:
+// the same as a rolled loop; NP > 0: exactly NP pairs without a branch (unused entries are never touched: r2 = -1).
+constexpr int kObstNP1 = 0;   // the rollout's NP (DESIGN §3b has the resource report of each variant)
+template <int N, int NP, bool MASK, class KC>
+__device__ __forceinline__ ObstMask chain_hits(const ObstR& o, const ChainState<N>& x, const KC& k) {
+    ObstMask m = 0;
+    bool any = false;
+    auto pair = [&](int p) {
+        const DiscPair d = load_pair(o, p);
+        f32x2 qX = d.cX, qY = d.cY;   // the pair's centres relative to link a's base
+#pragma unroll
+        for (int a = 0; a < N; ++a) {
+            const f32x2 cs = {get(x.c, a), get(x.s, a)};
+            const float L = k.p[kOffFk + a];
+            bool ha, hb;
+            seg_hits(qX, qY, cs, L, d.r2, ha, hb);
+            if constexpr (MASK) m |= ((ObstMask)ha << (16 * p + a)) | ((ObstMask)hb << (16 * p + 8 + a));
+            else any |= ha | hb;
+            if (a + 1 < N) {
+                qX = pfma(splat(-L), splat(cs.x), qX);
+                qY = pfma(splat(-L), splat(cs.y), qY);
+            }
+        }
+    };
+    if constexpr (NP < 0) {
+#pragma nounroll
+        for (int p = 0; 2 * p < o.n; ++p) pair(p);
+    } else {
+#pragma unroll
+        for (int p = 0; p < (NP ? NP : kObstPairs); ++p) {
+            if (NP == 0 && 2 * p >= o.n) break;
+            pair(p);
+        }
+    }
+    return MASK ? m : (ObstMask)any;
+}
+
+// The fp64 rollout: seg_hits' operations in doubles on the fp64 centres and r^2 (rec: cx[8], cy[8], r2[8] in LDS,
+// uniform addresses), disc by disc (nd is wave-uniform).
+template <int N, bool MASK>
+__device__ __forceinline__ ObstMask chain_hits_f64(const double* rec, int nd, const ChainStateD<N>& x, cdouble* k) {
+    ObstMask m = 0;
+    bool any = false;
+    for (int j = 0; j < nd; ++j) {
+        double qx = rec[j], qy = rec[MPPI_MAX_OBSTACLES + j];
+        const double r2 = rec[2 * MPPI_MAX_OBSTACLES + j];
+#pragma unroll
+        for (int a = 0; a < N; ++a) {
+            const double L = k[kOffFk + a];
+            const double s = fma(qy, x.s[a], qx * x.c[a]);
+            const double t = s < 0.0 ? 0.0 : (s > L ? L : s);
+            const double ox = fma(-t, x.c[a], qx), oy = fma(-t, x.s[a], qy);
+            const bool h = fma(oy, oy, ox * ox) < r2;
+            if constexpr (MASK) m |= (ObstMask)h << (8 * j + a);
+            else any |= h;
+            if (a + 1 < N) {
+                qx = fma(-L, x.c[a], qx);
+                qy = fma(-L, x.s[a], qy);
+            }
+        }
+    }
+    return MASK ? m : (ObstMask)any;
+}
+
+// What an obstacle-debug instance of the rollout kernel records for the first K samples
+// (mppi_chain_debug_obstacle_hits): mask[k][t] and dir[k][t][2 N] = (cos th_a at a, sin th_a at N + a), fp32.
+struct ObstDbg {
+    ObstMask* mask;
+    float* dir;
+    int K;
+};
+
 // The fused update's median filter runs over windows of kMedRun consecutive steps per thread: thread
 // (q, d) = (tid / N, tid % N) takes the windows of t = kMedRun q .. kMedRun q + 3 of column d.
 constexpr int kMedRun = 4;
@@ -586,10 +685,13 @@ struct alignas(16) WinRowD {
     double x, y, d1, d2;
 };
 // CLAMP: every sampled control is clipped in fp64 against the fp64 limits (cl.u_lo, cl.u_hi).
-template <int N, bool CLAMP>
+// OBST: every step's new state is tested against the discs (obd: chain_hits_f64's records, nd of them); *hits
+// receives the count of colliding states, the final one counted once more.  ODBG: the masks and directions go to od.
+template <int N, bool CLAMP, bool OBST = false, bool ODBG = false>
 __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const ChainStep* st, cdouble* kd,
                                                     const float* noise, int k, float exf, WinRowD* s_wind,
-                                                    int* slots, const ChainClampK& cl) {
+                                                    int* slots, const ChainClampK& cl, const double* obd = nullptr,
+                                                    int nd = 0, int* hits = nullptr, const ObstDbg& od = ObstDbg{}) {
     const int tid = threadIdx.x, K = c.K_local, T = c.T;
     if (tid < kSlots) {
         const double* r = st->wind[tid];
@@ -602,6 +704,8 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
     cdouble* ca = (cdouble*)&st->a[0][0];
     const int W = (int)st->ctr.z;
     double S = 0.0, ex = 0.0, ey = 0.0, e1 = 0.0, e2 = 0.0;
+    int nhit = 0;            // colliding states so far (OBST)
+    bool hit_last = false;   // the last step's flag: the final state counts once more
     float nx[N];
 #pragma unroll
     for (int d = 0; d < N; ++d) nx[d] = noise[(size_t)k * N + d];
@@ -617,6 +721,19 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
 #pragma unroll
         for (int d = 0; d < N; ++d) nx[d] = noise[((size_t)tn * K + k) * N + d];
         x.step(v, kd);
+        if constexpr (ODBG) {
+            if (k < od.K) {
+                od.mask[(size_t)k * T + t] = chain_hits_f64<N, true>(obd, nd, x, kd);
+#pragma unroll
+                for (int a = 0; a < N; ++a) {
+                    od.dir[((size_t)k * T + t) * 2 * N + a] = (float)x.c[a];
+                    od.dir[((size_t)k * T + t) * 2 * N + N + a] = (float)x.s[a];
+                }
+            }
+        } else if constexpr (OBST) {
+            hit_last = chain_hits_f64<N, false>(obd, nd, x, kd) != 0;
+            nhit += hit_last ? 1 : 0;
+        }
         double px, py;
         x.effector(kd, &px, &py);
         int best = 0;
@@ -638,6 +755,7 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
         e2 = x.dq[1] - r.d2;
         S += fma(kd[kOffSw], ex * ex, fma(kd[kOffSw + 1], ey * ey, fma(kd[kOffSw + 2], e1 * e1, kd[kOffSw + 3] * (e2 * e2)))) + g;
     }
+    if constexpr (OBST) *hits = nhit + (hit_last ? 1 : 0);
     // terminal cost, control.py:109
     return S + fma(kd[kOffTw], ex * ex, fma(kd[kOffTw + 1], ey * ey, fma(kd[kOffTw + 2], e1 * e1, kd[kOffTw + 3] * (e2 * e2))));
 }
@@ -712,11 +830,17 @@ __device__ __forceinline__ float elem(f32x2 v) {
 // CLAMP: the lane's pair of sampled controls is clipped (v_med3_f32) against its pair of fp32 limits, held in
 // four VGPRs for the whole horizon (they differ by lane, so neither can be a scalar operand), before the pad
 // factor: the pad link of an odd chain stays exactly 0 whatever the limits.
-template <int N, bool CLAMP>
+// OBST: lane p tests its own two links against the discs after every step.  The base of its pair is the quad's
+// exclusive prefix sum of fk (cos, sin) over the lanes below (the scan the dynamics use, DPP quad_perm); the
+// flag is OR-ed across the quad, so every lane of the quad keeps the sample's count and the owner's S carries it.
+// The pad link of an odd chain (and the links of lanes past the chain) has length 0 and sits at the end effector:
+// its comparisons are masked off, it never hits.  ODBG: the masks and directions go to od.
+template <int N, bool CLAMP, bool OBST = false, bool ODBG = false>
 __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const ChainStep* st, const float* dyn,
                                                    const float* noise, int k, float exf, float4* s_ua4,
                                                    float4* s_win, int* slots, unsigned long long* dbg,
-                                                   const ChainClampK& cl) {
+                                                   const ChainClampK& cl, const ObstR& ob = ObstR{}, int* hits = nullptr,
+                                                   const ObstDbg& od = ObstDbg{}) {
     static_assert(N <= 8, "four link pairs");
     // the column after which the search is placed: after 2 / 3 / 4 / 5 / 6 measured 77.0 / 76.6 / 77.6 / 75.3 /
     // 77.3 us at K = 16384 (one process, profiles/r13/chain_quad_search_at_ab.txt)
@@ -798,6 +922,53 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
 #pragma unroll
     for (int j = 0; j < kQPF; ++j) uar[j] = s_ua4[j * 4 + sub];
 
+    int nhit = 0;            // colliding states so far (OBST)
+    bool hit_last = false;   // the last step's flag: the final state counts once more
+    // the new state (C, Sn) of step t against the discs in use (a scalar branch per pair: ob.n is wave-uniform)
+    auto quad_hits = [&](int t) {
+        const bool live0 = a0 < N, live1 = a1 < N;   // pad links and lanes past the chain never hit
+        const f32x2 fx = fk2 * C, fy = fk2 * Sn;
+        const float bx = q_excl_prefix(fx.x + fx.y, m1), by = q_excl_prefix(fy.x + fy.y, m1);   // the pair's base
+        bool any = false;
+        ObstMask m = 0;
+#pragma unroll
+        for (int p = 0; p < kObstPairs; ++p) {
+            if (2 * p >= ob.n) break;
+            const DiscPair d = load_pair(ob, p);
+            f32x2 qX = d.cX - splat(bx), qY = d.cY - splat(by);
+            bool h0a, h0b, h1a, h1b;
+            seg_hits(qX, qY, f32x2{C.x, Sn.x}, fk2.x, d.r2, h0a, h0b);
+            qX = pfma(splat(-fk2.x), splat(C.x), qX);
+            qY = pfma(splat(-fk2.x), splat(Sn.x), qY);
+            seg_hits(qX, qY, f32x2{C.y, Sn.y}, fk2.y, d.r2, h1a, h1b);
+            h0a &= live0;
+            h0b &= live0;
+            h1a &= live1;
+            h1b &= live1;
+            if constexpr (ODBG)
+                m |= ((ObstMask)h0a << (16 * p + a0)) | ((ObstMask)h0b << (16 * p + 8 + a0)) |
+                     ((ObstMask)h1a << (16 * p + a1)) | ((ObstMask)h1b << (16 * p + 8 + a1));
+            else any |= (h0a | h0b) | (h1a | h1b);
+        }
+        if constexpr (ODBG) {
+            if (k < od.K) {
+                // (the mask buffer arrives zeroed; each lane adds the bits of its own links)
+                if (m) atomicOr(&od.mask[(size_t)k * T + t], m);
+                float* dr = od.dir + ((size_t)k * T + t) * 2 * N;
+                if (live0) {
+                    dr[a0] = C.x;
+                    dr[N + a0] = Sn.x;
+                }
+                if (live1) {
+                    dr[a1] = C.y;
+                    dr[N + a1] = Sn.y;
+                }
+            }
+        } else {
+            hit_last = q_sum(any ? 1.f : 0.f) != 0.f;
+            nhit += hit_last ? 1 : 0;
+        }
+    };
     double S = 0.0;
     f32x2 S2 = {0.f, 0.f};   // this lane's two stage-cost terms
     f32x2 G2 = {0.f, 0.f};   // this lane's (gamma u^T Sigma^-1) v terms
@@ -892,6 +1063,7 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
         THD = __builtin_elementwise_fma(f32x2{xa, xb}, splat(dt), THD);  // semi-implicit Euler (chain_oracle.py)
         TH = __builtin_elementwise_fma(THD, splat(dtr), TH);
         angles();
+        if constexpr (OBST) quad_hits(t);
         {   // the pending (previous state's) stage cost, control.py:174-185; the row is taken only now (the
             // asm needs TH, this step's last dynamics result)
             f32x2 rw = prw;
@@ -950,6 +1122,7 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
     S += (double)((S2.x + S2.y) + (G2.x + G2.y));
     const f32x2 te = tw2 * ee;
     S += (double)(te.x + te.y);
+    if constexpr (OBST) *hits = nhit + (hit_last ? 1 : 0);
     return q_sum_f64(S);
 }
 
@@ -958,15 +1131,26 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
 // each sample picked at each step, int32 [k][t].
 // CLAMP: the sampled controls are clipped to the torque limits cl (clamp_mode != 0) and, with cl.mode == 2, so
 // is the fused update's nominal; the CLAMP = false instantiations never read cl.
-template <int N, bool POLL, bool F64, int LPS, bool SLOTS = false, bool CLAMP = false>
+// OBST: every step's new state, and the final state once more, is tested against the discs of ob (staged in LDS by
+// one thread); the count of colliding states times ob.w is added to S once, in fp64, after the terminal cost.
+// Built with CLAMP only: without torque limits cl holds -+inf, the median and the fp64 compares return v untouched
+// and cl.mode = 0 clips no nominal.  The OBST = false instantiations never read ob.
+// ODBG (mppi_chain_debug_obstacle_hits; CLAMP and OBST): the same prologue and horizon, which record the masks and
+// directions of the first `flags` samples instead of counting (gslab: the masks, slab: the directions), and
+// nothing after the horizon.
+template <int N, bool POLL, bool F64, int LPS, bool SLOTS = false, bool CLAMP = false, bool OBST = false,
+          bool ODBG = false>
 __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) void chain_rollout_kernel(
     const ChainConst c, const ChainStep* __restrict__ st, const float* __restrict__ dyn,
     const float* __restrict__ noise, double* __restrict__ S_out, double* __restrict__ slab, double* __restrict__ gslab,
     unsigned* __restrict__ counters, double* __restrict__ partial_out, double* __restrict__ w_eps_out,
     ChainStep* __restrict__ nxt, unsigned flags, const XDesc xd, unsigned* __restrict__ epoch, unsigned* __restrict__ tmo,
-    unsigned long long* __restrict__ runmin, unsigned long long* __restrict__ dbg, const ChainClampK cl) {
+    unsigned long long* __restrict__ runmin, unsigned long long* __restrict__ dbg, const ChainClampK cl,
+    const ChainObstK ob) {
     static_assert(N <= kCMax && N >= 2, "links");
     static_assert(!(SLOTS && CLAMP), "the slot-recording instances are unclamped");
+    static_assert(CLAMP || !OBST, "the OBST kernels are built with CLAMP only");
+    static_assert(OBST || !ODBG, "the obstacle-debug instances are OBST kernels");
     __shared__ float4 s_win[kSlots];
     __shared__ KeyPair s_keys[kKeyPairs];
     __shared__ WinRowD s_wind[F64 ? kSlots : 1];
@@ -1006,11 +1190,39 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     double u_cur[kMedRun];
     if constexpr (!kLateNominal) chain_nominal_prefetch<N>(st, T, flags & MPPI_FLAG_FUSED_UPDATE, u_cur);
     double S = 0.0;
+    // OBST: the discs in LDS, published by the horizon's first barrier
+    ObstR od{};
+    const double* obd = nullptr;
+    int nd = 0;
+    if constexpr (OBST) {
+        nd = __builtin_amdgcn_readfirstlane(ob.n);
+        if constexpr (F64) {
+            __shared__ double s_obd[3 * MPPI_MAX_OBSTACLES];
+            if (tid == 0) {
+#pragma unroll
+                for (int j = 0; j < MPPI_MAX_OBSTACLES; ++j) {
+                    s_obd[j] = ob.cxd[j];
+                    s_obd[MPPI_MAX_OBSTACLES + j] = ob.cyd[j];
+                    s_obd[2 * MPPI_MAX_OBSTACLES + j] = ob.r2d[j];
+                }
+            }
+            obd = s_obd;
+        } else {
+            __shared__ float4 s_obst[2 * kObstPairs];
+            if (tid == 0) stage_obst(s_obst, ob);
+            od = ObstR{s_obst, nd};
+        }
+    }
+    ObstDbg odbg{};
+    if constexpr (ODBG) odbg = ObstDbg{reinterpret_cast<ObstMask*>(gslab), reinterpret_cast<float*>(slab), valid ? (int)flags : 0};
+    int hits = 0;   // colliding states of this sample, the final one counted twice (OBST)
     if constexpr (F64) {
-        S = chain_horizon_f64<N, CLAMP>(c, st, (cdouble*)(dyn + kDynF64Off), noise, k, exf, s_wind, slots, cl);
+        S = chain_horizon_f64<N, CLAMP, OBST, ODBG>(c, st, (cdouble*)(dyn + kDynF64Off), noise, k, exf, s_wind, slots, cl,
+                                                    obd, nd, &hits, odbg);
     } else if constexpr (LPS == 4) {
-        S = chain_horizon_q4<N, CLAMP>(c, st, dyn, noise, k, exf, s_ua4, s_win, slots, dbg, cl);
+        S = chain_horizon_q4<N, CLAMP, OBST, ODBG>(c, st, dyn, noise, k, exf, s_ua4, s_win, slots, dbg, cl, od, &hits, odbg);
     } else {
+    bool hit_last = false;
     if (tid < kSlots) s_win[tid] = st->win[tid];
     if constexpr (CLAMP) {
         if (tid < kCMax) s_vhi[tid] = dyn[kDynLimOff + kCMax + tid];
@@ -1047,7 +1259,9 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // Horizon loop (control.py:95-109 with the chain model), S in fp64.
     float S4 = 0.f;
     float ex = 0.f, ey = 0.f, e1 = 0.f, e2 = 0.f;
-    auto step = [&](int t, auto i_c) {
+    // (always_inline: with the OBST test in it the body passes the inliner's threshold, and a called step keeps its
+    // captures in scratch; the other instantiations were inlined already)
+    auto step = [&](int t, auto i_c) __attribute__((always_inline)) {
         constexpr int i = decltype(i_c)::value;
         float v[N];
         float g = 0.f;
@@ -1066,6 +1280,20 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             uring[i % kCPU][d] = cua[(t + kCPU) * 2 * kCMax + (d < N ? d : kCMax + d - N)];
         PIN_LOADS();
         x.step(v, kd);
+        if constexpr (ODBG) {
+            if (k < odbg.K) {
+                odbg.mask[(size_t)k * T + t] = chain_hits<N, kObstNP1, true>(od, x, kd);
+#pragma unroll
+                for (int a = 0; a < N; ++a) {
+                    odbg.dir[((size_t)k * T + t) * 2 * N + a] = get(x.c, a);
+                    odbg.dir[((size_t)k * T + t) * 2 * N + N + a] = get(x.s, a);
+                }
+            }
+        } else if constexpr (OBST) {
+            // on the (cos, sin) row pairs the step just produced, the ones effector() reads below
+            hit_last = chain_hits<N, kObstNP1, false>(od, x, kd) != 0;
+            hits += hit_last ? 1 : 0;
+        }
         float px, py;
         x.effector(kd, &px, &py);
         const unsigned j = sr.nearest(px, py);
@@ -1093,7 +1321,11 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }, std::make_integer_sequence<int, 3>{});
     S += (double)S4;
     S += (double)weighted_sq(ex, ey, e1, e2, c.dyn + kOffTw);  // terminal cost, control.py:109
+    if constexpr (OBST) hits += hit_last ? 1 : 0;              // the final state once more
     }
+    if constexpr (ODBG) return;
+    // the penalty in one fp64 multiply and add: the count is exact, so no order of summation can change it
+    if constexpr (OBST) S += ob.w * (double)hits;
 
     STAMP(1, NOW());
     if (S_out && owner) S_out[k] = S;
@@ -1351,6 +1583,8 @@ struct mppi_chain_ctx {
     mppi_host::Handoff hand;       // hand-off form, its buffers and the time-out words
     ChainConst kc;
     ChainClampK ck{};              // torque limits (mode 0: none)
+    ChainObstK ok{};               // workspace obstacles of the next launch (n = 0: none), mppi_chain_set_obstacles
+    int obst_per_cu = 0;           // occupancy of the context's OBST rollout kernel (workgroups per CU)
     mppi_host::DevBuf<ChainStep> d_step;      // [2] ping-pong
     int cur = 0;
     mppi_host::PinnedBuf<ChainStep> h_step;   // pinned staging
@@ -1383,7 +1617,7 @@ namespace {
 using mppi_host::fail;
 using mppi_host::launch_check;
 
-template <int N, bool P, bool F64, int LPS, bool CL>
+template <int N, bool P, bool F64, int LPS, bool CL, bool OB>
 void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise, double* S, double* part, ChainStep* nxt,
                     unsigned flags, int* slots = nullptr) {
     const mppi_host::Handoff& h = c->hand;
@@ -1392,12 +1626,12 @@ void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise,
             hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, true>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc,
                                cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags,
                                c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin,
-                               reinterpret_cast<unsigned long long*>(slots), c->ck);
+                               reinterpret_cast<unsigned long long*>(slots), c->ck, c->ok);
         return;
     }
-    hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, false, CL>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc,
-                       cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags, c->ex.xd,
-                       h.d_epoch, h.h_tmo.dev, c->d_runmin, c->d_dbg, c->ck);
+    hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, false, CL, OB>), dim3(c->nblocks), dim3(kCT), 0, c->stream,
+                       c->kc, cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags,
+                       c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin, c->d_dbg, c->ck, c->ok);
 }
 
 // the link counts with an instantiated kernel: f(N) for N = n as an integral constant
@@ -1406,19 +1640,23 @@ void with_links(int n, F&& f) {
     mppi_host::with_value<2, 3, 4, 5, 6, 7>(n, f);
 }
 
-// The instantiated rollout kernels: links x POLL x (fp64 at one lane per sample, fp32 at one or four) x CLAMP.
-// Calls f(n, poll, f64, lps, clamp), the context's instance as integral constants, in the hand-off form `poll`.
+// The instantiated rollout kernels: links x POLL x (fp64 at one lane per sample, fp32 at one or four) x (plain,
+// CLAMP, CLAMP + OBST).  Calls f(n, poll, f64, lps, clamp, obst), the context's instance as integral constants, in
+// the hand-off form `poll`.  With `obst` the CLAMP + OBST kernel, whether or not there are torque limits (without
+// them ChainClampK and the device copy of its fp32 limits hold -+inf, and clamp_mode 0 clips no nominal).
 template <class F>
-void with_rollout(const mppi_chain_ctx* c, bool poll, F&& f) {
+void with_rollout(const mppi_chain_ctx* c, bool poll, bool obst, F&& f) {
     using L1 = std::integral_constant<int, 1>;
     using L4 = std::integral_constant<int, 4>;
     with_links(c->n, [&](auto n) {
         mppi_host::with_bool(poll, [&](auto p) {
-            mppi_host::with_bool(c->ck.mode != 0, [&](auto cl) {
-                if (c->f64) f(n, p, std::true_type{}, L1{}, cl);
-                else if (c->lps == 4) f(n, p, std::false_type{}, L4{}, cl);
-                else f(n, p, std::false_type{}, L1{}, cl);
-            });
+            auto form = [&](auto cl, auto ob) {
+                if (c->f64) f(n, p, std::true_type{}, L1{}, cl, ob);
+                else if (c->lps == 4) f(n, p, std::false_type{}, L4{}, cl, ob);
+                else f(n, p, std::false_type{}, L1{}, cl, ob);
+            };
+            if (obst) form(std::true_type{}, std::true_type{});
+            else mppi_host::with_bool(c->ck.mode != 0, [&](auto cl) { form(cl, std::false_type{}); });
         });
     });
 }
@@ -1473,9 +1711,14 @@ int alloc(mppi_chain_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     int ncu = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-    with_rollout(c, true, [&](auto n, auto p, auto f64, auto lps, auto cl) {   // always of the POLL form
+    with_rollout(c, true, false, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {   // always of the POLL form
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl>, kCT, 0);
+            &per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob>, kCT, 0);
+    });
+    // the kernel a launch with discs goes through: mppi_chain_set_obstacles refuses discs if it does not fit a CU
+    with_rollout(c, true, true, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &c->obst_per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob>, kCT, 0);
     });
     // behind the counters: the per-CU ticket words of the issue fairness (mppi_device.h)
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + c->cfg.T * c->n, kCuSlots)) return rc;
@@ -1616,6 +1859,10 @@ int mppi_chain_ctx_create(const mppi_chain_config* cfg, int device, void* stream
         ck.v_hi[d] = (float)ck.u_hi[d];
     }
 
+    for (int j = 0; j < MPPI_MAX_OBSTACLES; ++j) {   // no discs
+        c->ok.r2[j] = -1.f;
+        c->ok.r2d[j] = -1.0;
+    }
     for (int i = 0; i < n; ++i)
         for (int j = 0; j <= i; ++j) c->chol.L[i * kCMax + j] = (float)(Lc[i][j] * kBoxMullerScale);   // box_muller's constant
     if (int rc = alloc(c.get())) return rc;
@@ -1703,8 +1950,8 @@ int chain_rollout(mppi_chain_ctx* c, const float* noise_dev, double* S_dev, doub
     }
     const ChainStep* cur = c->d_step + c->cur;
     ChainStep* nxt = c->d_step + (c->cur ^ 1);
-    with_rollout(c, c->hand.poll, [&](auto n, auto p, auto f64, auto lps, auto cl) {
-        launch_rollout<n, p, f64, lps, cl>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots);
+    with_rollout(c, c->hand.poll, c->ok.n > 0, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {
+        launch_rollout<n, p, f64, lps, cl, ob>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots);
     });
     if (int rc = launch_check("chain_rollout_kernel")) return rc;
     note_update(c, flags);
@@ -1730,7 +1977,59 @@ int mppi_chain_debug_slots(mppi_chain_ctx* c, const float* noise_dev, double* S_
     if (!c || !noise_dev || !slots_dev) return fail(MPPI_E_ARG, "null argument");
     if (c->n != kCDebugN) return fail(MPPI_E_ARG, "slot recording is built for the 7-link chain only");
     if (c->ck.mode != 0) return fail(MPPI_E_ARG, "slot recording is built without torque limits (clamp_mode 0 only)");
+    if (c->ok.n > 0) return fail(MPPI_E_ARG, "slot recording is built without obstacles (remove the discs first)");
     return chain_rollout(c, noise_dev, S_dev, nullptr, 0u, slots_dev);
+}
+
+int mppi_chain_set_obstacles(mppi_chain_ctx* c, int n, const double* discs, double cost) {
+    if (!c) return fail(MPPI_E_ARG, "null context");
+    if (n < 0 || n > MPPI_MAX_OBSTACLES) return fail(MPPI_E_ARG, "obstacles: n must be in [0, 8]");
+    if (n > 0 && !discs) return fail(MPPI_E_ARG, "obstacles: null discs");
+    if (!(cost >= 0.0) || isinf(cost)) return fail(MPPI_E_ARG, "obstacles: the cost must be finite and >= 0");
+    if (n > 0 && c->obst_per_cu < 1) return fail(MPPI_E_ARG, "obstacles: the rollout kernel with discs does not fit a CU");
+    ChainObstK k{};
+    for (int j = 0; j < MPPI_MAX_OBSTACLES; ++j) {   // below every squared distance: never touched
+        k.r2[j] = -1.f;
+        k.r2d[j] = -1.0;
+    }
+    for (int j = 0; j < n; ++j) {
+        const double cx = discs[3 * j], cy = discs[3 * j + 1], r = discs[3 * j + 2];
+        if (!isfinite((float)cx) || !isfinite((float)cy)) return fail(MPPI_E_ARG, "obstacles: a centre is not finite");
+        if (!(r >= 0.0)) return fail(MPPI_E_ARG, "obstacles: a radius is NaN or negative");
+        k.cx[j] = (float)cx;
+        k.cy[j] = (float)cy;
+        k.r2[j] = (float)(r * r);
+        k.cxd[j] = cx;
+        k.cyd[j] = cy;
+        k.r2d[j] = r * r;
+    }
+    k.w = cost;
+    k.n = n;
+    c->ok = k;   // read by the next launch of any kind (a kernel argument, by value): no device call
+    return MPPI_OK;
+}
+
+int mppi_chain_debug_obstacle_hits(mppi_chain_ctx* c, const float* noise_dev, int K, unsigned long long* mask_dev,
+                                   float* dir_dev) {
+    if (!c || !noise_dev || !mask_dev || !dir_dev || K < 1 || K > c->cfg.K_local) return fail(MPPI_E_ARG, "bad argument");
+    if (c->obst_per_cu < 1) return fail(MPPI_E_ARG, "obstacles: the rollout kernel with discs does not fit a CU");
+    // the quad form adds each lane's bits to its sample's mask
+    HIP_TRY(hipMemsetAsync(mask_dev, 0, (size_t)K * c->cfg.T * sizeof(unsigned long long), c->stream));
+    // the context's own form of the OBST kernel, counter hand-off (it ends before any hand-off), over the
+    // workgroups that hold the first K samples; the masks travel in gslab's place, the directions in slab's and K
+    // in flags'; no timeline buffer
+    const int blocks = (int)(((long long)K * c->lps + kCT - 1) / kCT);
+    const mppi_host::Handoff& h = c->hand;
+    const ChainStep* cur = c->d_step + c->cur;
+    with_rollout(c, false, true, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {
+        if constexpr (ob && !p)   // (with_rollout also instantiates this lambda for the other kernels)
+            hipLaunchKernelGGL((chain_rollout_kernel<n, p, f64, lps, false, cl, ob, true>), dim3(blocks), dim3(kCT), 0,
+                               c->stream, c->kc, cur, c->d_dyn, noise_dev, (double*)nullptr,
+                               reinterpret_cast<double*>(dir_dev), reinterpret_cast<double*>(mask_dev), h.d_counter,
+                               (double*)nullptr, (double*)nullptr, (ChainStep*)nullptr, (unsigned)K, c->ex.xd, h.d_epoch,
+                               h.h_tmo.dev, c->d_runmin, (unsigned long long*)nullptr, c->ck, c->ok);
+    });
+    return launch_check("chain_rollout_kernel (obstacle debug)");
 }
 
 

@@ -536,6 +536,53 @@ __device__ __forceinline__ void fair_priority(unsigned parity) {
         __builtin_amdgcn_s_setprio(0);
 }
 
+// ---- workspace obstacles: what the arm's and the chain's collision tests share (mppi_set_obstacles,
+// mppi_chain_set_obstacles).  The discs of a launch as the test reads them: in LDS, two discs per 32-byte record
+// (cx, cx', cy, cy', r2, r2', 0, 0), read back with uniform addresses (a broadcast).  Scalar registers would be the
+// natural home of wave-uniform values, but the rollout kernels have none to spare (they spill ~90 already, into
+// VGPR lanes), and an LDS read takes no VALU issue slot where a v_readlane per operand does.
+constexpr int kObstPairs = MPPI_MAX_OBSTACLES / 2;
+struct ObstR {
+    const float4* rec;   // [2 * kObstPairs] in LDS
+    int n;               // scalar
+};
+struct DiscPair {
+    f32x2 cX, cY, r2;
+};
+// One thread writes the records (constant kernel-argument offsets: a run-time index into the by-value struct would
+// send it through a private copy); the caller's barrier publishes them.  OB: the kernel's by-value disc argument
+// (fp32 cx, cy, r2 of MPPI_MAX_OBSTACLES entries).
+template <class OB>
+__device__ __forceinline__ void stage_obst(float4* rec, const OB& ob) {
+#pragma unroll
+    for (int p = 0; p < kObstPairs; ++p) {
+        rec[2 * p] = make_float4(ob.cx[2 * p], ob.cx[2 * p + 1], ob.cy[2 * p], ob.cy[2 * p + 1]);
+        rec[2 * p + 1] = make_float4(ob.r2[2 * p], ob.r2[2 * p + 1], 0.f, 0.f);
+    }
+}
+__device__ __forceinline__ DiscPair load_pair(const ObstR& o, int p) {
+    const float4 a = o.rec[2 * p], b = o.rec[2 * p + 1];
+    return DiscPair{f32x2{a.x, a.y}, f32x2{a.z, a.w}, f32x2{b.x, b.y}};
+}
+
+// Does a link touch a disc: two discs (the halves of pX, pY, r2) against the segment from the origin of
+// (pX, pY) — the disc centres relative to the link's base — along the unit direction cs = (cos, sin), length L.
+// The well-conditioned form: project the centre on the direction, clip the parameter to [0, L] with one
+// v_med3_f32 (0 <= L), subtract the foot point and square the offset; nothing cancels at the magnitude of the
+// centre.  Five roundings on the way to d (two in s, one in each offset component, two in the sum of their
+// squares), each at magnitude <= |centre| + L.  Every product-sum is an explicit fma, so a rollout and its debug
+// kernel (mppi_debug_obstacle_hits, mppi_chain_debug_obstacle_hits) evaluate the same operations whatever the
+// compiler would contract.
+__device__ __forceinline__ void seg_hits(f32x2 pX, f32x2 pY, f32x2 cs, float L, f32x2 r2, bool& ha, bool& hb) {
+    const f32x2 s = __builtin_elementwise_fma(pY, f32x2{cs.y, cs.y}, pX * f32x2{cs.x, cs.x});
+    const f32x2 t = {__builtin_amdgcn_fmed3f(s.x, 0.f, L), __builtin_amdgcn_fmed3f(s.y, 0.f, L)};
+    const f32x2 oX = __builtin_elementwise_fma(-t, f32x2{cs.x, cs.x}, pX);
+    const f32x2 oY = __builtin_elementwise_fma(-t, f32x2{cs.y, cs.y}, pY);
+    const f32x2 d = __builtin_elementwise_fma(oY, oY, oX * oX);
+    ha = d.x < r2.x;
+    hb = d.y < r2.y;
+}
+
 }  // namespace mppi
 
 #include "mppi_merge.h"

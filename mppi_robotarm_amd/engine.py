@@ -41,7 +41,7 @@ class _Engine:
     # the entry points both ABIs have under their prefix; resolved once at construction into self._c_<name>
     CALLS = ("ctx_create", "ctx_destroy", "set_stream", "set_step_inputs", "rollout", "merge_partials",
              "exchange_handle", "exchange_attach", "get_weighted_noise", "get_nominal", "rollout_traj",
-             "wait_outputs", "optimal_traj_host", "noise_philox", "sync")
+             "wait_outputs", "optimal_traj_host", "noise_philox", "sync", "set_obstacles")
     # wait_outputs first follows torch's current stream (the arm's does not: no stream synchronise on its path)
     WAIT_FOLLOWS_STREAM = False
 
@@ -67,6 +67,7 @@ class _Engine:
                                        C.byref(ctx)), prefix + "ctx_create")
         self._ctx = ctx
         self.partial_len = 2 + self.dim_u * self.T
+        self.obstacles, self.obstacle_cost = np.zeros((0, 3)), 0.0   # what set_obstacles last gave the context
 
     # -- torque limits ------------------------------------------------------
     @staticmethod
@@ -88,6 +89,40 @@ class _Engine:
                 cfg.u_min[d], cfg.u_max[d] = float(lo[d]), float(hi[d])
         self.u_min = None if not cfg.clamp_mode else np.array(cfg.u_min[:dim_u])
         self.u_max = None if not cfg.clamp_mode else np.array(cfg.u_max[:dim_u])
+
+    # -- workspace obstacles (both ABIs: mppi_set_obstacles, mppi_chain_set_obstacles) --
+    @staticmethod
+    def check_obstacles(discs, cost) -> tuple[np.ndarray, float]:
+        """(discs as a C-contiguous fp64 (n, 3) array of (cx, cy, r), cost as a float), or ValueError: at most
+        MPPI_MAX_OBSTACLES rows of three values, finite centres, r >= 0 (not NaN), a finite cost >= 0.  None or
+        an empty sequence: no discs, (0, 3)."""
+        try:
+            a = np.zeros((0, 3)) if discs is None else np.array(discs, dtype=np.float64, ndmin=1)
+            w = float(cost)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"obstacles: {e}") from None
+        if a.size == 0:
+            a = np.zeros((0, 3))
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"obstacles must be (n, 3) rows of (cx, cy, r), got shape {a.shape}")
+        if a.shape[0] > N.MPPI_MAX_OBSTACLES:
+            raise ValueError(f"at most {N.MPPI_MAX_OBSTACLES} obstacles, got {a.shape[0]}")
+        if not np.all(np.isfinite(a[:, :2].astype(np.float32))):
+            raise ValueError("obstacles: a centre is not finite")
+        if not np.all(a[:, 2] >= 0.0):
+            raise ValueError("obstacles: a radius is NaN or negative")
+        if not (w >= 0.0 and math.isfinite(w)):
+            raise ValueError("obstacle_cost must be finite and >= 0")
+        return np.ascontiguousarray(a), w
+
+    def set_obstacles(self, discs, cost: float = 1.0e10) -> None:
+        """Discs (n, 3) of (cx, cy, r), n <= 8, that no link may touch, and the cost a colliding step adds
+        to its sample's S (the final state once more): <prefix>set_obstacles.  In effect from the next launch of
+        any kind; None or no rows removes them.  No device call.  ValueError for a bad shape or value."""
+        a, w = self.check_obstacles(discs, cost)
+        N.check(self._c_set_obstacles(self._ctx, a.shape[0], _dptr(a) if a.shape[0] else None, w),
+                self._prefix + "set_obstacles")
+        self.obstacles, self.obstacle_cost = a, w
 
     # -- lifetime -----------------------------------------------------------
     def close(self) -> None:
@@ -344,7 +379,6 @@ class RolloutEngine(_Engine):
         N.check(self._lib.mppi_ctx_handoff(self._ctx, C.byref(poll)), "mppi_ctx_handoff")
         # in-launch hand-off of the workgroup partials: "poll" (tagged granules) or "counter"
         self.handoff = "poll" if poll.value else "counter"
-        self.obstacles, self.obstacle_cost = np.zeros((0, 3)), 0.0   # what set_obstacles last gave the context
 
     def pending(self) -> bool:
         """Diagnostics: the last fused launch took the deferred form and its step is not finished yet
@@ -356,40 +390,7 @@ class RolloutEngine(_Engine):
     def merge(self, partials: torch.Tensor, n: int, fused_update: bool = False, host_out: bool = False) -> None:
         super().merge(partials, n, fused_update, N.MPPI_FLAG_HOST_OUT if host_out else 0)   # host_out: the arm only
 
-    # -- workspace obstacles --------------------------------------------------
-    @staticmethod
-    def check_obstacles(discs, cost) -> tuple[np.ndarray, float]:
-        """(discs as a C-contiguous fp64 (n, 3) array of (cx, cy, r), cost as a float), or ValueError: at most
-        MPPI_MAX_OBSTACLES rows of three values, finite centres, r >= 0 (not NaN), a finite cost >= 0.  None or
-        an empty sequence: no discs, (0, 3)."""
-        try:
-            a = np.zeros((0, 3)) if discs is None else np.array(discs, dtype=np.float64, ndmin=1)
-            w = float(cost)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"obstacles: {e}") from None
-        if a.size == 0:
-            a = np.zeros((0, 3))
-        if a.ndim != 2 or a.shape[1] != 3:
-            raise ValueError(f"obstacles must be (n, 3) rows of (cx, cy, r), got shape {a.shape}")
-        if a.shape[0] > N.MPPI_MAX_OBSTACLES:
-            raise ValueError(f"at most {N.MPPI_MAX_OBSTACLES} obstacles, got {a.shape[0]}")
-        if not np.all(np.isfinite(a[:, :2].astype(np.float32))):
-            raise ValueError("obstacles: a centre is not finite")
-        if not np.all(a[:, 2] >= 0.0):
-            raise ValueError("obstacles: a radius is NaN or negative")
-        if not (w >= 0.0 and math.isfinite(w)):
-            raise ValueError("obstacle_cost must be finite and >= 0")
-        return np.ascontiguousarray(a), w
-
-    def set_obstacles(self, discs, cost: float = 1.0e10) -> None:
-        """Discs (n, 3) of (cx, cy, r), n <= 8, that neither link may touch, and the cost a colliding step adds
-        to its sample's S (the final state once more): mppi_set_obstacles.  In effect from the next launch of
-        any kind; None or no rows removes them.  No device call.  ValueError for a bad shape or value."""
-        a, w = self.check_obstacles(discs, cost)
-        N.check(self._lib.mppi_set_obstacles(self._ctx, a.shape[0], _dptr(a) if a.shape[0] else None, w),
-                "mppi_set_obstacles")
-        self.obstacles, self.obstacle_cost = a, w
-
+    # -- workspace obstacles (check_obstacles, set_obstacles: _Engine) ----------
     def obstacle_hits(self, noise: torch.Tensor, K: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Tests: the rollout's collision test per sample and step (mppi_debug_obstacle_hits) -> (mask (K, T)
         uint32: bit 2j link 1 touches disc j, bit 2j + 1 link 2 does; dir (K, T, 4) fp32: the (cos q1, sin q1,
