@@ -368,6 +368,26 @@ int mppi_sync(mppi_ctx *ctx);
 #define MPPI_MAX_OBSTACLES 8
 int mppi_set_obstacles(mppi_ctx *ctx, int n, const double *discs, double cost);
 
+/* Moving obstacles: mppi_set_obstacles with a velocity per disc, vel[n][2] row-major
+ * (vx, vy) in m/s, constant over the horizon of one call; vel = NULL: every disc at
+ * rest, which is mppi_set_obstacles.  discs holds the positions at the observed
+ * state x0.  Rollout step t (0-based) produces the state at time (t + 1) delta_t, and
+ * that state is tested against the discs centred at c + v (t + 1) delta_t; the final
+ * state's extra count uses the centres at T delta_t, those of step T - 1.  S =
+ * S_track + cost * hits as before.  The caller advances the positions between
+ * calls: the controller does not integrate the world.  On the device the centre of
+ * step t is fma(v, tau_t, c) in fp32, tau_t the fp32 rounding of the fp64 (t + 1)
+ * delta_t, read by the rollout from a per-step table in LDS.
+ *
+ * Everything else is mppi_set_obstacles': no device call, in effect from the next
+ * launch of any kind, a by-value kernel input (a captured graph freezes discs and
+ * velocities), n = 0 restores the kernels from before any discs.  MPPI_E_ARG also
+ * for a non-finite velocity and for a centre that is not finite in fp32 at time
+ * T delta_t; the discs in effect are then kept.  mppi_debug_obstacle_hits
+ * evaluates the moving discs. */
+int mppi_set_moving_obstacles(mppi_ctx *ctx, int n, const double *discs, const double *vel,
+                              double cost);
+
 /* Tests: the collision test of the first K samples at every step as the rollout
  * evaluates it (the same fp32 dynamics and the same device function) on the
  * current step inputs, discs and noise_dev ([T][K_local][2] fp32).
@@ -542,6 +562,21 @@ int mppi_chain_debug_slots(mppi_chain_ctx *ctx, const float *noise_dev, double *
  * outside 0..MPPI_MAX_OBSTACLES, a NaN or negative r, a non-finite centre, and a NaN,
  * negative or infinite cost; the discs in effect are then kept. */
 int mppi_chain_set_obstacles(mppi_chain_ctx *ctx, int n, const double *discs, double cost);
+
+/* Moving obstacles for the chain: mppi_set_moving_obstacles' definition on every
+ * link.  vel[n][2] row-major (vx, vy) in m/s, constant over the horizon of one call,
+ * NULL: every disc at rest, which is mppi_chain_set_obstacles; discs holds the
+ * positions at the observed state.  Rollout step t tests its new state against the
+ * discs centred at c + v (t + 1) delta_t, the final state's extra count uses the
+ * centres of step T - 1.  In the rollout's own precision: the centre of step t is one
+ * fma(v, tau_t, c), in fp32 with tau_t the fp32 rounding of the fp64 (t + 1) delta_t,
+ * in fp64 for precision 1.  The rules are mppi_chain_set_obstacles'; MPPI_E_ARG also
+ * for a non-finite velocity and for a centre that is not finite in fp32 at time
+ * T delta_t, and it refuses as mppi_chain_set_obstacles does when the kernel with
+ * moving discs does not fit a CU; the discs in effect are then kept.
+ * mppi_chain_debug_obstacle_hits evaluates the moving discs. */
+int mppi_chain_set_moving_obstacles(mppi_chain_ctx *ctx, int n, const double *discs,
+                                    const double *vel, double cost);
 
 /* Tests: the collision test of the first K samples at every step as the context's
  * rollout evaluates it (the same kernel: its precision, its lanes per sample, its

@@ -40,14 +40,15 @@ EXPORTS = (
     "mppi_dropin_tick_launch", "mppi_dropin_tick_wait",
     "mppi_noise_philox",
     "mppi_sync", "mppi_debug_set_buffer", "mppi_debug_pending",
-    "mppi_debug_nearest", "mppi_debug_dropin_times", "mppi_set_obstacles", "mppi_debug_obstacle_hits",
+    "mppi_debug_nearest", "mppi_debug_dropin_times", "mppi_set_obstacles", "mppi_set_moving_obstacles",
+    "mppi_debug_obstacle_hits",
     "mppi_chain_ctx_create", "mppi_chain_ctx_destroy", "mppi_chain_set_stream", "mppi_chain_ctx_info",
     "mppi_chain_set_step_inputs", "mppi_chain_rollout", "mppi_chain_merge_partials", "mppi_chain_exchange_handle",
     "mppi_chain_exchange_attach",
     "mppi_chain_get_weighted_noise", "mppi_chain_get_nominal", "mppi_chain_rollout_traj",
     "mppi_chain_noise_philox", "mppi_chain_sync", "mppi_chain_debug_set_buffer", "mppi_chain_debug_slots",
     "mppi_chain_wait_outputs", "mppi_chain_optimal_traj_host", "mppi_chain_last_eta",
-    "mppi_chain_set_obstacles", "mppi_chain_debug_obstacle_hits",
+    "mppi_chain_set_obstacles", "mppi_chain_set_moving_obstacles", "mppi_chain_debug_obstacle_hits",
     "mppi_config_init", "mppi_chain_config_init",
     "mppi_np_ctx_create", "mppi_np_ctx_destroy", "mppi_np_plan", "mppi_np_set_jumps", "mppi_np_draw",
     "mppi_np_draw_result", "mppi_readback_create", "mppi_readback_destroy", "mppi_readback_run",
@@ -178,6 +179,7 @@ def open_library(path: str):
         "mppi_debug_dropin_times": ([vp, dp], C.c_int),
         "mppi_debug_nearest": ([vp, fp, C.c_int, vp, fp], C.c_int),
         "mppi_set_obstacles": ([vp, C.c_int, dp, C.c_double], C.c_int),
+        "mppi_set_moving_obstacles": ([vp, C.c_int, dp, dp, C.c_double], C.c_int),
         "mppi_debug_obstacle_hits": ([vp, fp, C.c_int, vp, fp], C.c_int),
         "mppi_chain_ctx_create": ([C.POINTER(ChainConfigC), C.c_int, vp, C.POINTER(vp)], C.c_int),
         "mppi_chain_ctx_destroy": ([vp], None),
@@ -199,6 +201,7 @@ def open_library(path: str):
         "mppi_chain_optimal_traj_host": ([vp, dp, dp, dp], C.c_int),
         "mppi_chain_last_eta": ([vp, dp], C.c_int),
         "mppi_chain_set_obstacles": ([vp, C.c_int, dp, C.c_double], C.c_int),
+        "mppi_chain_set_moving_obstacles": ([vp, C.c_int, dp, dp, C.c_double], C.c_int),
         "mppi_chain_debug_obstacle_hits": ([vp, fp, C.c_int, vp, fp], C.c_int),
         "mppi_config_init": ([C.POINTER(ConfigC)], None),
         "mppi_np_ctx_create": ([C.c_int, vp, C.POINTER(vp)], C.c_int),

@@ -196,7 +196,10 @@ class ChainMPPIController(MPPIControllerBase):
 
     ``obstacles`` / ``obstacle_cost``: up to eight discs ``(cx, cy, r)`` that no link may touch, as on the arm
     controller: every colliding step of a sample, and its final state once more, adds ``obstacle_cost`` to its
-    cost (mppi_chain_set_obstacles).  Plain attributes, compared by value on every call, so they may be edited in
+    cost (mppi_chain_set_obstacles).  ``obstacle_velocities``: ``(n, 2)`` rows of ``(vx, vy)`` in m/s, one per disc,
+    constant over the horizon of a call, or ``None`` for discs at rest (mppi_chain_set_moving_obstacles): ``obstacles``
+    then holds the positions at the observed state, rollout step ``t`` tests its new state against the discs at
+    ``c + v (t + 1) delta_t``, and the caller advances ``obstacles`` between calls.  Plain attributes, compared by value on every call, so they may be edited in
     place or rebound between calls; a bad value raises ValueError before anything is drawn or moved.  Every
     engine a step runs on (``precision="auto"``'s fp64 one, every rank's of a process group) gets them before its
     launch."""
@@ -212,7 +215,7 @@ class ChainMPPIController(MPPIControllerBase):
                  u_init=None, device: int | None = None, verbose: bool = False, noise: str = "numpy", seed: int = 0,
                  process_group=None, exchange: str = "auto", precision: str = "auto",
                  numpy_noise_on_device: bool = True, u_min=None, u_max=None, obstacles=None,
-                 obstacle_cost: float = 1.0e10) -> None:
+                 obstacle_cost: float = 1.0e10, obstacle_velocities=None) -> None:
         self.chain = chain
         if precision not in ("auto", "f32", "f64"):
             raise ValueError("precision must be 'auto', 'f32' or 'f64'")
@@ -234,7 +237,8 @@ class ChainMPPIController(MPPIControllerBase):
         self._limits()                          # u_min <= u_max
         self.obstacles = obstacles              # (n, 3) array-like of discs (cx, cy, r), n <= 8, or None
         self.obstacle_cost = obstacle_cost      # added to S per colliding step (and once for the final state)
-        self._obst_checked = None               # the last (obstacles bytes, cost) that passed the checks
+        self.obstacle_velocities = obstacle_velocities   # (n, 2) array-like of (vx, vy) in m/s, or None: at rest
+        self._obst_checked = None               # the last (obstacles bytes, cost, velocities) that passed the checks
         self._okey = None                       # this call's key (_obstacle_key), for _device_step
         self._obstacle_key()
         self._slots = {}               # rollout precision -> the parked state of its engine (_SLOT fields)

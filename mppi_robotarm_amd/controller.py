@@ -37,7 +37,12 @@ the updated nominal is clipped too, exactly as ``_g`` clipping in place would),
 link may touch: every colliding step of a sample, and its final state once more,
 adds ``obstacle_cost`` to its cost, the reference with ``_c`` and ``_phi``
 returning ``... + obstacle_cost * collides(x)``; plain attributes, re-read on
-every call, so they may move between calls),
+every call, so they may move between calls), ``obstacle_velocities`` (``(n, 2)``
+rows of ``(vx, vy)`` in m/s, one per disc, constant over the horizon of a call,
+or ``None`` for discs at rest: ``obstacles`` then holds the positions at the
+observed state, and the state rollout step ``t`` produces is tested against the
+discs at ``c + v (t + 1) delta_t``; the caller advances ``obstacles`` between
+calls; a plain attribute compared by value like ``obstacles``),
 ``process_group`` (shard the samples over the ranks of a
 torch.distributed group), ``exchange`` (with a process group: "auto" = the
 in-launch exchange, one launch per rank per step, when its one-step self-check
@@ -103,6 +108,7 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
             u_max=None,
             obstacles=None,
             obstacle_cost: float = 1.0e10,
+            obstacle_velocities=None,
             process_group=None,
             exchange: str = "auto",
             host_update: bool = False,
@@ -139,7 +145,8 @@ class MPPIControllerForPathTracking(MPPIControllerBase):
         self._limits()                          # u_min <= u_max
         self.obstacles = obstacles              # (n, 3) array-like of discs (cx, cy, r), n <= 8, or None
         self.obstacle_cost = obstacle_cost      # added to S per colliding step (and once for the final state)
-        self._obst_checked = None               # the last (obstacles bytes, cost) that passed the checks
+        self.obstacle_velocities = obstacle_velocities   # (n, 2) array-like of (vx, vy) in m/s, or None: at rest
+        self._obst_checked = None               # the last (obstacles bytes, cost, velocities) that passed the checks
         self._okey = None                       # this call's key, for _tick (whose signature tests stub)
         self._obstacle_key()
         self._bound = None             # what the engine's drop-in tick is bound to (_bind_key)

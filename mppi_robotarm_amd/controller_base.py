@@ -230,33 +230,55 @@ class MPPIControllerBase:
 
     # ------------------------------------------------------------ obstacles (both drop-ins)
     def _obstacle_key(self):
-        """self.obstacles / self.obstacle_cost by value: None without discs, else (the (n, 3) fp64 bytes, the
-        cost), checked (ValueError for a bad shape or value).  Compared on every call, the bound tick's too,
-        so a rebind and an in-place edit are both seen.  A subclass sets the two plain attributes and
-        ``_obst_checked = None`` (the last key that passed the checks)."""
-        if self.obstacles is None:
-            return None
-        try:
-            a = np.array(self.obstacles, dtype=np.float64, ndmin=1)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"obstacles: {e}") from None
-        if a.size == 0:
+        """self.obstacles / self.obstacle_cost / self.obstacle_velocities by value: None without discs, else (the
+        (n, 3) fp64 bytes, the cost[, the (n, 2) velocity bytes]), checked (ValueError for a bad shape or value,
+        and for velocities without discs).  Compared on every call, the bound tick's too, so a rebind and an
+        in-place edit are both seen.  A subclass sets the plain attributes and ``_obst_checked = None`` (the
+        last key that passed the checks)."""
+        vel = getattr(self, "obstacle_velocities", None)   # (a controller without moving obstacles has none)
+        a = None
+        if self.obstacles is not None:
+            try:
+                a = np.array(self.obstacles, dtype=np.float64, ndmin=1)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"obstacles: {e}") from None
+        if a is None or a.size == 0:
+            if vel is not None:
+                raise ValueError("obstacle_velocities given without obstacles")
             return None
         try:
             key = (a.shape, a.tobytes(), float(self.obstacle_cost))
         except (TypeError, ValueError) as e:
             raise ValueError(f"obstacle_cost: {e}") from None
+        if vel is not None:
+            # by value, beside the discs: a rebind and an in-place edit are both seen; a key of three entries is
+            # the static one, so None and discs at rest given as zeros are told apart only by the call they take
+            try:
+                v = np.array(vel, dtype=np.float64, ndmin=1)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"obstacle_velocities: {e}") from None
+            key += (v.shape, v.tobytes())
         if key != self._obst_checked:
-            _Engine.check_obstacles(a, self.obstacle_cost)
+            a, _ = _Engine.check_obstacles(a, self.obstacle_cost)
+            _Engine.check_velocities(vel, a.shape[0])
             self._obst_checked = key
         return key
 
     def _push_obstacles(self, eng, key) -> None:
-        """Give the engine this call's discs unless it holds them already (no device call either way)."""
+        """Give the engine this call's discs and velocities unless it holds them already (no device call either
+        way)."""
         have = eng.obstacles
         have = (have.shape, have.tobytes(), eng.obstacle_cost) if have.shape[0] else None
+        hv = getattr(eng, "obstacle_velocities", None)
+        if have is not None and hv is not None:
+            have += (hv.shape, hv.tobytes())
         if key != have:
-            eng.set_obstacles(None if key is None else self.obstacles, self.obstacle_cost)
+            if key is None:
+                eng.set_obstacles(None, self.obstacle_cost)
+            elif getattr(self, "obstacle_velocities", None) is None:
+                eng.set_obstacles(self.obstacles, self.obstacle_cost)
+            else:
+                eng.set_obstacles(self.obstacles, self.obstacle_cost, velocities=self.obstacle_velocities)
 
     # ------------------------------------------------------------ engine
     def _shard(self):

@@ -111,7 +111,16 @@ struct ChainObstK {
     double cxd[MPPI_MAX_OBSTACLES], cyd[MPPI_MAX_OBSTACLES], r2d[MPPI_MAX_OBSTACLES];
     double w;
     int n;
+    // moving discs (mppi_chain_set_moving_obstacles), behind everything there was: velocities in m/s, constant over
+    // the horizon (0 at rest), in fp32 and fp64 like the centres; the fp64 time step; and whether any velocity is
+    // not zero (the host's choice of the MOVE kernels; the kernels do not read it)
+    float vx[MPPI_MAX_OBSTACLES], vy[MPPI_MAX_OBSTACLES];
+    double vxd[MPPI_MAX_OBSTACLES], vyd[MPPI_MAX_OBSTACLES];
+    double dt;
+    int moving;
 };
+// The fp64 rollout's records of one step: cx[8], cy[8], r2[8] (chain_hits_f64)
+constexpr int kObstRowD = 3 * MPPI_MAX_OBSTACLES;
 // what mppi_chain_debug_obstacle_hits records: bit 8 j + a of a mask is link a against disc j
 using ObstMask = unsigned long long;
 
@@ -687,7 +696,8 @@ struct alignas(16) WinRowD {
 // CLAMP: every sampled control is clipped in fp64 against the fp64 limits (cl.u_lo, cl.u_hi).
 // OBST: every step's new state is tested against the discs (obd: chain_hits_f64's records, nd of them); *hits
 // receives the count of colliding states, the final one counted once more.  ODBG: the masks and directions go to od.
-template <int N, bool CLAMP, bool OBST = false, bool ODBG = false>
+// MOVE: obd holds one row of records per step (the discs at c + v (t + 1) dt), and step t reads row t.
+template <int N, bool CLAMP, bool OBST = false, bool ODBG = false, bool MOVE = false>
 __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const ChainStep* st, cdouble* kd,
                                                     const float* noise, int k, float exf, WinRowD* s_wind,
                                                     int* slots, const ChainClampK& cl, const double* obd = nullptr,
@@ -721,9 +731,10 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
 #pragma unroll
         for (int d = 0; d < N; ++d) nx[d] = noise[((size_t)tn * K + k) * N + d];
         x.step(v, kd);
+        const double* obt = MOVE ? obd + t * kObstRowD : obd;
         if constexpr (ODBG) {
             if (k < od.K) {
-                od.mask[(size_t)k * T + t] = chain_hits_f64<N, true>(obd, nd, x, kd);
+                od.mask[(size_t)k * T + t] = chain_hits_f64<N, true>(obt, nd, x, kd);
 #pragma unroll
                 for (int a = 0; a < N; ++a) {
                     od.dir[((size_t)k * T + t) * 2 * N + a] = (float)x.c[a];
@@ -731,7 +742,7 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
                 }
             }
         } else if constexpr (OBST) {
-            hit_last = chain_hits_f64<N, false>(obd, nd, x, kd) != 0;
+            hit_last = chain_hits_f64<N, false>(obt, nd, x, kd) != 0;
             nhit += hit_last ? 1 : 0;
         }
         double px, py;
@@ -835,7 +846,8 @@ __device__ __forceinline__ float elem(f32x2 v) {
 // flag is OR-ed across the quad, so every lane of the quad keeps the sample's count and the owner's S carries it.
 // The pad link of an odd chain (and the links of lanes past the chain) has length 0 and sits at the end effector:
 // its comparisons are masked off, it never hits.  ODBG: the masks and directions go to od.
-template <int N, bool CLAMP, bool OBST = false, bool ODBG = false>
+// MOVE: ob.rec holds one row of records per step (stage_obst_row), and step t reads row t.
+template <int N, bool CLAMP, bool OBST = false, bool ODBG = false, bool MOVE = false>
 __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const ChainStep* st, const float* dyn,
                                                    const float* noise, int k, float exf, float4* s_ua4,
                                                    float4* s_win, int* slots, unsigned long long* dbg,
@@ -934,7 +946,7 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
 #pragma unroll
         for (int p = 0; p < kObstPairs; ++p) {
             if (2 * p >= ob.n) break;
-            const DiscPair d = load_pair(ob, p);
+            const DiscPair d = load_pair(MOVE ? ObstR{ob.rec + t * kObstRow, ob.n} : ob, p);
             f32x2 qX = d.cX - splat(bx), qY = d.cY - splat(by);
             bool h0a, h0b, h1a, h1b;
             seg_hits(qX, qY, f32x2{C.x, Sn.x}, fk2.x, d.r2, h0a, h0b);
@@ -1139,7 +1151,7 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
 // directions of the first `flags` samples instead of counting (gslab: the masks, slab: the directions), and
 // nothing after the horizon.
 template <int N, bool POLL, bool F64, int LPS, bool SLOTS = false, bool CLAMP = false, bool OBST = false,
-          bool ODBG = false>
+          bool ODBG = false, bool MOVE = false>
 __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) void chain_rollout_kernel(
     const ChainConst c, const ChainStep* __restrict__ st, const float* __restrict__ dyn,
     const float* __restrict__ noise, double* __restrict__ S_out, double* __restrict__ slab, double* __restrict__ gslab,
@@ -1151,6 +1163,8 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     static_assert(!(SLOTS && CLAMP), "the slot-recording instances are unclamped");
     static_assert(CLAMP || !OBST, "the OBST kernels are built with CLAMP only");
     static_assert(OBST || !ODBG, "the obstacle-debug instances are OBST kernels");
+    static_assert(OBST || !MOVE, "moving discs are discs");
+    static_assert(kMaxT <= kCT, "thread t stages step t's disc records");
     __shared__ float4 s_win[kSlots];
     __shared__ KeyPair s_keys[kKeyPairs];
     __shared__ WinRowD s_wind[F64 ? kSlots : 1];
@@ -1196,8 +1210,30 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int nd = 0;
     if constexpr (OBST) {
         nd = __builtin_amdgcn_readfirstlane(ob.n);
-        if constexpr (F64) {
-            __shared__ double s_obd[3 * MPPI_MAX_OBSTACLES];
+        if constexpr (MOVE) {
+            // a row of records per step, the discs where that step's new state meets them: thread t writes step t's,
+            // every centre one explicit fma of the velocity, the time (t + 1) dt and the centre at x0 (in the
+            // rollout's precision; fp32: stage_obst_row, mppi_device.h, with the time rounded once from fp64)
+            if constexpr (F64) {
+                __shared__ double s_obd[kMaxT * kObstRowD];
+                if (tid < T) {
+                    const double tau = (double)(tid + 1) * ob.dt;
+                    double* row = s_obd + tid * kObstRowD;
+#pragma unroll
+                    for (int j = 0; j < MPPI_MAX_OBSTACLES; ++j) {
+                        row[j] = fma(ob.vxd[j], tau, ob.cxd[j]);
+                        row[MPPI_MAX_OBSTACLES + j] = fma(ob.vyd[j], tau, ob.cyd[j]);
+                        row[2 * MPPI_MAX_OBSTACLES + j] = ob.r2d[j];
+                    }
+                }
+                obd = s_obd;
+            } else {
+                __shared__ float4 s_obst[kMaxT * kObstRow];
+                if (tid < T) stage_obst_row(s_obst + tid * kObstRow, ob, tid);
+                od = ObstR{s_obst, nd};
+            }
+        } else if constexpr (F64) {
+            __shared__ double s_obd[kObstRowD];
             if (tid == 0) {
 #pragma unroll
                 for (int j = 0; j < MPPI_MAX_OBSTACLES; ++j) {
@@ -1217,10 +1253,10 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if constexpr (ODBG) odbg = ObstDbg{reinterpret_cast<ObstMask*>(gslab), reinterpret_cast<float*>(slab), valid ? (int)flags : 0};
     int hits = 0;   // colliding states of this sample, the final one counted twice (OBST)
     if constexpr (F64) {
-        S = chain_horizon_f64<N, CLAMP, OBST, ODBG>(c, st, (cdouble*)(dyn + kDynF64Off), noise, k, exf, s_wind, slots, cl,
+        S = chain_horizon_f64<N, CLAMP, OBST, ODBG, MOVE>(c, st, (cdouble*)(dyn + kDynF64Off), noise, k, exf, s_wind, slots, cl,
                                                     obd, nd, &hits, odbg);
     } else if constexpr (LPS == 4) {
-        S = chain_horizon_q4<N, CLAMP, OBST, ODBG>(c, st, dyn, noise, k, exf, s_ua4, s_win, slots, dbg, cl, od, &hits, odbg);
+        S = chain_horizon_q4<N, CLAMP, OBST, ODBG, MOVE>(c, st, dyn, noise, k, exf, s_ua4, s_win, slots, dbg, cl, od, &hits, odbg);
     } else {
     bool hit_last = false;
     if (tid < kSlots) s_win[tid] = st->win[tid];
@@ -1280,9 +1316,10 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             uring[i % kCPU][d] = cua[(t + kCPU) * 2 * kCMax + (d < N ? d : kCMax + d - N)];
         PIN_LOADS();
         x.step(v, kd);
+        const ObstR odt = MOVE ? ObstR{od.rec + t * kObstRow, od.n} : od;   // MOVE: step t's row of records
         if constexpr (ODBG) {
             if (k < odbg.K) {
-                odbg.mask[(size_t)k * T + t] = chain_hits<N, kObstNP1, true>(od, x, kd);
+                odbg.mask[(size_t)k * T + t] = chain_hits<N, kObstNP1, true>(odt, x, kd);
 #pragma unroll
                 for (int a = 0; a < N; ++a) {
                     odbg.dir[((size_t)k * T + t) * 2 * N + a] = get(x.c, a);
@@ -1291,7 +1328,7 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         } else if constexpr (OBST) {
             // on the (cos, sin) row pairs the step just produced, the ones effector() reads below
-            hit_last = chain_hits<N, kObstNP1, false>(od, x, kd) != 0;
+            hit_last = chain_hits<N, kObstNP1, false>(odt, x, kd) != 0;
             hits += hit_last ? 1 : 0;
         }
         float px, py;
@@ -1585,6 +1622,7 @@ struct mppi_chain_ctx {
     ChainClampK ck{};              // torque limits (mode 0: none)
     ChainObstK ok{};               // workspace obstacles of the next launch (n = 0: none), mppi_chain_set_obstacles
     int obst_per_cu = 0;           // occupancy of the context's OBST rollout kernel (workgroups per CU)
+    int move_per_cu = 0;           // ... and of its MOVE form
     mppi_host::DevBuf<ChainStep> d_step;      // [2] ping-pong
     int cur = 0;
     mppi_host::PinnedBuf<ChainStep> h_step;   // pinned staging
@@ -1628,6 +1666,15 @@ void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise,
                                c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin,
                                reinterpret_cast<unsigned long long*>(slots), c->ck, c->ok);
         return;
+    }
+    if constexpr (OB) {
+        if (c->ok.moving) {   // a disc has a velocity: the MOVE form, which reads a row of disc records per step
+            hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, false, CL, OB, false, true>), dim3(c->nblocks),
+                               dim3(kCT), 0, c->stream, c->kc, cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter,
+                               part, c->d_weps, nxt, flags, c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin, c->d_dbg, c->ck,
+                               c->ok);
+            return;
+        }
     }
     hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, false, CL, OB>), dim3(c->nblocks), dim3(kCT), 0, c->stream,
                        c->kc, cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags,
@@ -1719,6 +1766,10 @@ int alloc(mppi_chain_ctx* c) {
     with_rollout(c, true, true, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
             &c->obst_per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob>, kCT, 0);
+        // ... and with moving discs (the per-step records: 16 KB of LDS more, 24 KB in fp64)
+        if constexpr (ob)
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                &c->move_per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob, false, true>, kCT, 0);
     });
     // behind the counters: the per-CU ticket words of the issue fairness (mppi_device.h)
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + c->cfg.T * c->n, kCuSlots)) return rc;
@@ -1982,6 +2033,10 @@ int mppi_chain_debug_slots(mppi_chain_ctx* c, const float* noise_dev, double* S_
 }
 
 int mppi_chain_set_obstacles(mppi_chain_ctx* c, int n, const double* discs, double cost) {
+    return mppi_chain_set_moving_obstacles(c, n, discs, nullptr, cost);
+}
+
+int mppi_chain_set_moving_obstacles(mppi_chain_ctx* c, int n, const double* discs, const double* vel, double cost) {
     if (!c) return fail(MPPI_E_ARG, "null context");
     if (n < 0 || n > MPPI_MAX_OBSTACLES) return fail(MPPI_E_ARG, "obstacles: n must be in [0, 8]");
     if (n > 0 && !discs) return fail(MPPI_E_ARG, "obstacles: null discs");
@@ -2002,7 +2057,22 @@ int mppi_chain_set_obstacles(mppi_chain_ctx* c, int n, const double* discs, doub
         k.cxd[j] = cx;
         k.cyd[j] = cy;
         k.r2d[j] = r * r;
+        if (!vel) continue;
+        const double vx = vel[2 * j], vy = vel[2 * j + 1];
+        if (!isfinite((float)vx) || !isfinite((float)vy)) return fail(MPPI_E_ARG, "obstacles: a velocity is not finite");
+        k.vx[j] = (float)vx;
+        k.vy[j] = (float)vy;
+        k.vxd[j] = vx;
+        k.vyd[j] = vy;
+        if (k.vx[j] != 0.f || k.vy[j] != 0.f) k.moving = 1;   // else the kernels of discs at rest, as vel = NULL
+        // the last row of the kernels' table (step T - 1), the farthest the disc gets
+        const float tau = (float)((double)c->cfg.T * c->cfg.delta_t);
+        if (!isfinite(fmaf(k.vx[j], tau, k.cx[j])) || !isfinite(fmaf(k.vy[j], tau, k.cy[j])))
+            return fail(MPPI_E_ARG, "obstacles: a centre is not finite at the end of the horizon");
     }
+    if (k.moving && c->move_per_cu < 1)
+        return fail(MPPI_E_ARG, "obstacles: the rollout kernel with moving discs does not fit a CU");
+    k.dt = c->cfg.delta_t;
     k.w = cost;
     k.n = n;
     c->ok = k;   // read by the next launch of any kind (a kernel argument, by value): no device call
@@ -2012,10 +2082,12 @@ int mppi_chain_set_obstacles(mppi_chain_ctx* c, int n, const double* discs, doub
 int mppi_chain_debug_obstacle_hits(mppi_chain_ctx* c, const float* noise_dev, int K, unsigned long long* mask_dev,
                                    float* dir_dev) {
     if (!c || !noise_dev || !mask_dev || !dir_dev || K < 1 || K > c->cfg.K_local) return fail(MPPI_E_ARG, "bad argument");
-    if (c->obst_per_cu < 1) return fail(MPPI_E_ARG, "obstacles: the rollout kernel with discs does not fit a CU");
+    if (c->obst_per_cu < 1 || c->move_per_cu < 1)
+        return fail(MPPI_E_ARG, "obstacles: the rollout kernel with discs does not fit a CU");
     // the quad form adds each lane's bits to its sample's mask
     HIP_TRY(hipMemsetAsync(mask_dev, 0, (size_t)K * c->cfg.T * sizeof(unsigned long long), c->stream));
-    // the context's own form of the OBST kernel, counter hand-off (it ends before any hand-off), over the
+    // the context's own form of the OBST kernel, always with a row of disc records per step (at rest the rows are
+    // equal: fma(0, tau, c) = c), counter hand-off (it ends before any hand-off), over the
     // workgroups that hold the first K samples; the masks travel in gslab's place, the directions in slab's and K
     // in flags'; no timeline buffer
     const int blocks = (int)(((long long)K * c->lps + kCT - 1) / kCT);
@@ -2023,7 +2095,7 @@ int mppi_chain_debug_obstacle_hits(mppi_chain_ctx* c, const float* noise_dev, in
     const ChainStep* cur = c->d_step + c->cur;
     with_rollout(c, false, true, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {
         if constexpr (ob && !p)   // (with_rollout also instantiates this lambda for the other kernels)
-            hipLaunchKernelGGL((chain_rollout_kernel<n, p, f64, lps, false, cl, ob, true>), dim3(blocks), dim3(kCT), 0,
+            hipLaunchKernelGGL((chain_rollout_kernel<n, p, f64, lps, false, cl, ob, true, true>), dim3(blocks), dim3(kCT), 0,
                                c->stream, c->kc, cur, c->d_dyn, noise_dev, (double*)nullptr,
                                reinterpret_cast<double*>(dir_dev), reinterpret_cast<double*>(mask_dev), h.d_counter,
                                (double*)nullptr, (double*)nullptr, (ChainStep*)nullptr, (unsigned)K, c->ex.xd, h.d_epoch,

@@ -560,6 +560,25 @@ __device__ __forceinline__ void stage_obst(float4* rec, const OB& ob) {
         rec[2 * p + 1] = make_float4(ob.r2[2 * p], ob.r2[2 * p + 1], 0.f, 0.f);
     }
 }
+// Moving discs (mppi_set_moving_obstacles): one row of records per rollout step, kObstRow float4 each, so the
+// horizon loop reads step t's discs at an address that walks with the step and gains no arithmetic.  The calling
+// thread writes step t's kObstRow records to rec: the centres at the time of the state that step produces, c + v tau
+// with tau the fp32 rounding of the fp64 (t + 1) dt, one explicit fma per coordinate (so a rollout and its debug
+// kernel agree); at rest (v = 0) the fma returns c, and every row is the row stage_obst writes.  OB: as stage_obst,
+// with vx, vy and the fp64 dt.
+constexpr int kObstRow = 2 * kObstPairs;
+template <class OB>
+__device__ __forceinline__ void stage_obst_row(float4* rec, const OB& ob, int t) {
+    const float tau = (float)((double)(t + 1) * ob.dt);
+#pragma unroll
+    for (int p = 0; p < kObstPairs; ++p) {
+        rec[2 * p] = make_float4(__builtin_fmaf(ob.vx[2 * p], tau, ob.cx[2 * p]),
+                                 __builtin_fmaf(ob.vx[2 * p + 1], tau, ob.cx[2 * p + 1]),
+                                 __builtin_fmaf(ob.vy[2 * p], tau, ob.cy[2 * p]),
+                                 __builtin_fmaf(ob.vy[2 * p + 1], tau, ob.cy[2 * p + 1]));
+        rec[2 * p + 1] = make_float4(ob.r2[2 * p], ob.r2[2 * p + 1], 0.f, 0.f);
+    }
+}
 __device__ __forceinline__ DiscPair load_pair(const ObstR& o, int p) {
     const float4 a = o.rec[2 * p], b = o.rec[2 * p + 1];
     return DiscPair{f32x2{a.x, a.y}, f32x2{a.z, a.w}, f32x2{b.x, b.y}};

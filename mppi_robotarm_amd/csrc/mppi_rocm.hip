@@ -34,6 +34,9 @@
 //    against up to eight discs after every step, on the (cos, sin) pairs the step just produced, count the
 //    colliding steps per sample in an integer and add cost x count to S once, in fp64.  The discs travel in
 //    ObstK, the last argument after ClampK; a context without discs launches the kernels it launched before.
+//  * moving obstacles (mppi_set_moving_obstacles): a velocity per disc, constant over the horizon; the MOVE
+//    instantiations read step t's discs, moved to c + v (t + 1) dt, from a per-step table that the prologue lays
+//    behind each step's constants in LDS, so the horizon loop gains no instruction.  Discs at rest launch OBST.
 //  * merge_kernel: the same merge over the all-gathered per-device partials
 //    (multi-GPU), traj_kernel: trajectory re-roll (control.py:129-145),
 //    philox_noise_kernel: counter-based Gaussian noise.
@@ -107,6 +110,12 @@ struct ObstK {
     float r2[MPPI_MAX_OBSTACLES];                           // r^2 (fp64 product, rounded once)
     double w;
     int n;
+    // moving discs (mppi_set_moving_obstacles), behind everything there was: velocities in m/s, constant over the
+    // horizon (0 at rest), the fp64 time step the per-step table's times are rounded from, and whether any velocity
+    // is not zero (the host's choice of the MOVE kernels; the kernels do not read it)
+    float vx[MPPI_MAX_OBSTACLES], vy[MPPI_MAX_OBSTACLES];
+    double dt;
+    int moving;
 };
 
 // One semi-implicit Euler step of _F (control.py:234-263) in closed form:
@@ -332,7 +341,7 @@ struct HostOut {
 // DEFER (the deferred finish, run by every workgroup of the next launch): the fp32 rows (u_t, a_t) also go to s_ua,
 // the LDS rows the horizon loop reads (rows T .. T + kPF - 1 repeat row T - 1); only a workgroup with `store`
 // writes nxt and upd; there are no host outputs (a launch with them finishes its step itself), so no barrier.
-template <int NT, bool CLAMP, bool DEFER = false>
+template <int NT, bool CLAMP, bool DEFER = false, int UAS = 1>
 __device__ void nominal_update_block(DevStep* nxt, const KConst& c, Scratch& sm, double u_src, double u_first,
                                      float* upd, HostOut ho, const ClampK& cl, bool publish = true,
                                      float4* s_ua = nullptr, bool store = true) {
@@ -368,9 +377,9 @@ __device__ void nominal_update_block(DevStep* nxt, const KConst& c, Scratch& sm,
                 const float4 row = make_float4((float)u0, (float)u1, (float)a0, (float)a1);
                 if (store) nxt->ua[t] = row;
                 if constexpr (DEFER) {
-                    s_ua[t] = row;
+                    s_ua[t * UAS] = row;
                     if (t == T - 1)
-                        for (int p = 0; p < kPF; ++p) s_ua[T + p] = row;
+                        for (int p = 0; p < kPF; ++p) s_ua[(T + p) * UAS] = row;
                 }
             }
         }
@@ -390,7 +399,7 @@ __device__ void nominal_update_block(DevStep* nxt, const KConst& c, Scratch& sm,
 // the one workgroup of finalize_kernel) also writes what the step leaves in global memory: nxt, w_eps_out, upd.
 // st: the nominal the step ran from.  l_row: kDirectRows ints of LDS.  Every thread must call it; it ends behind
 // a barrier for everything but s_ua (the caller's next barrier).
-template <int NT, bool CLAMP>
+template <int NT, bool CLAMP, int UAS = 1>
 __device__ __forceinline__ void deferred_finish(const KConst& c, const double* rows, const DevStep* st, DevStep* nxt,
                                                 double* w_eps_out, float* upd, const ClampK& cl, Scratch& sm,
                                                 int* l_row, float4* s_ua, bool store) {
@@ -399,7 +408,8 @@ __device__ __forceinline__ void deferred_finish(const KConst& c, const double* r
     const RowGeo geo(2 * c.T);
     deferred_merge<NT>(rows_rsrc(rows, c.nblocks * (geo.stride + 1) * 8), c.nblocks, geo, c.inv_lambda, sm, l_row,
                        store ? w_eps_out : nullptr);
-    nominal_update_block<NT, CLAMP, true>(nxt, c, sm, u_cur, u_first, upd, HostOut{nullptr, 0u}, cl, false, s_ua, store);
+    nominal_update_block<NT, CLAMP, true, UAS>(nxt, c, sm, u_cur, u_first, upd, HostOut{nullptr, 0u}, cl, false, s_ua,
+                                               store);
 }
 
 // ------------------------------------------------------------ rollout kernel
@@ -412,6 +422,9 @@ __device__ __forceinline__ void deferred_finish(const KConst& c, const double* r
 // colliding states times ob.w joins S after the terminal cost.  Every lane of a sample tests every disc, so S
 // does not depend on LPS.  Instantiated with CLAMP only: without torque limits the limits are -+inf, which the
 // median passes v through untouched.
+// MOVE (with OBST; the host picks it when a disc has a velocity): step t's new state is tested against the discs
+// at c + v (t + 1) dt, read from the per-step records in s_ua (stage_obst_row), and the final state once more
+// against step T - 1's.  The OBST instantiations without it carry no trace of it.
 // DEFER (the deferred form of a fused step in the device-resident loop; counter-form rows, so with !POLL only): the
 // launch ends once every workgroup has stored its row {rho_b, eta_b, N_b} into `slab`; it has no hand-off, no
 // merge and no update of its own.  Instead, when flags carries kFlagPending, its prologue finishes the PREVIOUS
@@ -419,7 +432,7 @@ __device__ __forceinline__ void deferred_finish(const KConst& c, const double* r
 // step ran from, and this launch rolls out from the updated one, which every workgroup computes for itself into
 // s_ua while workgroup 0 also stores it to nxt (with w_eps_out and upd) for the launch after this one.  The other
 // instantiations carry no trace of it.
-template <int LPS, int NT, bool POLL, bool CLAMP, bool OBST, bool DEFER = false>
+template <int LPS, int NT, bool POLL, bool CLAMP, bool OBST, bool DEFER = false, bool MOVE = false>
 __global__ __launch_bounds__(NT) void rollout_kernel(
     const KConst c, const StepStatic ss, const DevStep* __restrict__ st, const float2* __restrict__ noise,
     double* __restrict__ S_out, double* __restrict__ slab, double* __restrict__ gslab,
@@ -428,10 +441,16 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     float* __restrict__ upd, const HostOut ho, unsigned long long* __restrict__ dbg, const ClampK cl,
     const ObstK ob) {
     static_assert(CLAMP || !OBST, "the OBST kernels are built with CLAMP only");
+    static_assert(OBST || !MOVE, "moving discs are discs");
     static_assert(!DEFER || !POLL, "the deferred form leaves plain rows");
     static_assert(!DEFER || NT >= kDirectRows, "s_k holds the deferred merge's row list");
     __shared__ float4 s_win[kSlots];
-    __shared__ float4 s_ua[kMaxT + kPF];   // per-step constants (u_t, a_t); rows >= T repeat row T - 1
+    // per-step constants (u_t, a_t); rows >= T repeat row T - 1.  MOVE: a row is UAS records, the step's constants
+    // and then the disc records of that step (mppi_device.h, stage_obst_row), so the one offset that walks the
+    // constants (ua_off below) reaches the step's discs at compile-time offsets, and moving discs add no
+    // instruction to the horizon loop
+    constexpr int UAS = MOVE ? 1 + kObstRow : 1;
+    __shared__ float4 s_ua[(kMaxT + kPF) * UAS];
     __shared__ double s_redd[NT / 64];
     __shared__ int s_cnt[NT / 64];
     __shared__ int s_k[NT];
@@ -466,7 +485,7 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     if constexpr (DEFER) {
         // the previous launch's step, finished here behind the noise rows already in flight (wave-uniform branch)
         pending = (flags & kFlagPending) != 0;
-        if (pending) deferred_finish<NT, CLAMP>(c, gslab, st, nxt, w_eps_out, upd, cl, sm, s_k, s_ua, blockIdx.x == 0);
+        if (pending) deferred_finish<NT, CLAMP, UAS>(c, gslab, st, nxt, w_eps_out, upd, cl, sm, s_k, s_ua, blockIdx.x == 0);
         STAMP(10, NOW());
     }
     // window row for the LDS copy: loaded unconditionally (a load inside the
@@ -479,7 +498,11 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     DynK dk = make_dynk(c, sr.cx, sr.cy);
     if constexpr (CLAMP) dynk_limits(dk, cl);
     ObstR od{};
-    if constexpr (OBST) {
+    if constexpr (MOVE) {
+        // the discs of every step (stage_obst_row: moved by their velocities), behind that step's constants in s_ua
+        if (tid < T) stage_obst_row(s_ua + tid * UAS + 1, ob, tid);   // published by the barrier below
+        od = ObstR{s_ua + 1, __builtin_amdgcn_readfirstlane(ob.n)};
+    } else if constexpr (OBST) {
         __shared__ float4 s_obst[2 * kObstPairs];
         if (tid == 0) stage_obst(s_obst, ob);   // published by the barrier below
         od = ObstR{s_obst, __builtin_amdgcn_readfirstlane(ob.n)};
@@ -489,12 +512,12 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
     // the per-step constants go to LDS: the ring reads them there, so no scalar
     // load shares lgkmcnt with the deferred row lookup below
     if (!pending)
-        for (int i = tid; i < T + kPF; i += NT) s_ua[i] = st->ua[i < T ? i : T - 1];
+        for (int i = tid; i < T + kPF; i += NT) s_ua[i * UAS] = st->ua[i < T ? i : T - 1];
     if (tid < kSlots) s_win[tid] = wrow;
     __syncthreads();
     float4 uring[kPF];  // per-step constants (u_t, a_t), uniform
 #pragma unroll
-    for (int j = 0; j < kPF; ++j) uring[j] = s_ua[j < T ? j : T - 1];
+    for (int j = 0; j < kPF; ++j) uring[j] = s_ua[(j < T ? j : T - 1) * UAS];
 
     // Horizon loop (control.py:95-109): v = u + eps -> _F -> end effector ->
     // nearest waypoint -> stage cost + control cost, S in fp64.
@@ -555,8 +578,9 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
         const int tl = t + kPF < T ? t + kPF : T - 1;
         ring[slot] = np[(size_t)tl * K];
         uring[slot] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_ua) + ua_off +
-                                                       (kPF + slot) * (int)sizeof(float4));
-        if (slot == kPF - 1) ua_off += kPF * (int)sizeof(float4);   // slot == t % kPF at every call
+                                                       (kPF + slot) * UAS * (int)sizeof(float4));
+        // slot == t % kPF at every call (MOVE: advanced below, behind the step's disc reads)
+        if (!MOVE && slot == kPF - 1) ua_off += kPF * UAS * (int)sizeof(float4);
         PIN_LOADS();
         arm_step(x, v, dk);
         if (h) {
@@ -568,7 +592,16 @@ __global__ __launch_bounds__(NT) void rollout_kernel(
         }
         if constexpr (OBST) {
             // on the (cos, sin) pairs the step just produced, the ones arm_fk reads below: no transcendental
-            hit_last = obst_any<NP>(od, x.cs1, x.cs12, dk.fk);
+            if constexpr (MOVE) {
+                // against step t's discs: the records behind the step's constants in s_ua
+                const ObstR ot{reinterpret_cast<const float4*>(reinterpret_cast<const char*>(od.rec) + ua_off +
+                                                               slot * UAS * (int)sizeof(float4)),
+                               od.n};
+                hit_last = obst_any<NP>(ot, x.cs1, x.cs12, dk.fk);
+                if (slot == kPF - 1) ua_off += kPF * UAS * (int)sizeof(float4);
+            } else {
+                hit_last = obst_any<NP>(od, x.cs1, x.cs12, dk.fk);
+            }
             hits += hit_last ? 1 : 0;
         }
         pp = arm_fk(x, dk);   // control.py:178-179
@@ -885,10 +918,10 @@ __global__ __launch_bounds__(kThreads) void obstacle_debug_kernel(const KConst c
     arm_init(x, ss.x0);
     DynK dk = make_dynk(c, 0.f, 0.f);
     dynk_limits(dk, cl);
-    __shared__ float4 s_obst[2 * kObstPairs];
-    if (threadIdx.x == 0) stage_obst(s_obst, ob);
+    __shared__ float4 s_obst[kMaxT * kObstRow];
+    if ((int)threadIdx.x < T) stage_obst_row(s_obst + threadIdx.x * kObstRow, ob, threadIdx.x);
     __syncthreads();
-    const ObstR od{s_obst, __builtin_amdgcn_readfirstlane(ob.n)};
+    const int nd = __builtin_amdgcn_readfirstlane(ob.n);
     if (k >= Kn) return;
     for (int t = 0; t < T; ++t) {
         const float4 ua = st->ua[t];
@@ -896,7 +929,7 @@ __global__ __launch_bounds__(kThreads) void obstacle_debug_kernel(const KConst c
         f32x2 v = __builtin_elementwise_fma(splat(exf), f32x2{ua.x, ua.y}, f32x2{e.x, e.y});
         v = clamp_v(v, dk);   // as the OBST kernels: always through the median (-+inf without limits)
         arm_step(x, v, dk);
-        mask[(size_t)k * T + t] = obst_mask(od, x.cs1, x.cs12, dk.fk);
+        mask[(size_t)k * T + t] = obst_mask(ObstR{s_obst + t * kObstRow, nd}, x.cs1, x.cs12, dk.fk);
         dir[(size_t)k * T + t] = make_float4(x.cs1.x, x.cs1.y, x.cs12.x, x.cs12.y);
     }
 }
@@ -983,18 +1016,20 @@ using mppi_host::with_bool;
 using mppi_host::with_value;
 
 // The instantiated rollout kernels: LPS in {1, 2, 4, 8, 16} x NT in {256, 512} x POLL x (plain, CLAMP,
-// CLAMP + OBST).  Calls f(lps, nt, poll, clamp, obst), the instance of the context's next launch as integral
-// constants, in the hand-off form `poll`.  With discs set the launch goes through the CLAMP + OBST kernel
-// whether or not there are torque limits (without them ClampK holds -+inf, and clamp_mode 0 clips no nominal).
+// CLAMP + OBST, CLAMP + OBST + MOVE).  Calls f(lps, nt, poll, clamp, obst, move), the instance of the context's
+// next launch as integral constants, in the hand-off form `poll`.  With discs set the launch goes through the
+// CLAMP + OBST kernel whether or not there are torque limits (without them ClampK holds -+inf, and clamp_mode 0
+// clips no nominal), and through its MOVE form when a disc has a velocity.
 template <class F>
 void with_rollout(const mppi_ctx* c, bool poll, F&& f) {
     with_value<1, 2, 4, 8, 16>(c->lps, [&](auto lps) {
         with_value<256, 512>(c->nt, [&](auto nt) {
             with_bool(poll, [&](auto p) {
                 if (c->ok.n > 0)
-                    f(lps, nt, p, std::true_type{}, std::true_type{});
+                    with_bool(c->ok.moving != 0, [&](auto mv) { f(lps, nt, p, std::true_type{}, std::true_type{}, mv); });
                 else
-                    with_bool(c->ck.mode != 0, [&](auto cl) { f(lps, nt, p, cl, std::false_type{}); });
+                    with_bool(c->ck.mode != 0,
+                              [&](auto cl) { f(lps, nt, p, cl, std::false_type{}, std::false_type{}); });
             });
         });
     });
@@ -1082,9 +1117,16 @@ int alloc(mppi_ctx* c) {
     int ncu = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
     // of the kernel the context will launch (the CLAMP form holds two more register pairs), always its POLL form
-    with_rollout(c, true, [&](auto lps, auto nt, auto p, auto cl, auto ob) {
-        const void* f = (const void*)rollout_kernel<lps, nt, p, cl, ob>;
+    with_rollout(c, true, [&](auto lps, auto nt, auto p, auto cl, auto ob, auto mv) {
+        const void* f = (const void*)rollout_kernel<lps, nt, p, cl, ob, false, mv>;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, nt, 0) != hipSuccess) per_cu = 0;
+        // ... and of the MOVE form a later mppi_set_moving_obstacles may switch it to (the per-step disc table,
+        // 18 KB of LDS, and more registers).  Handoff::plan reads per_cu only as ">= 1" (the poll form needs every
+        // workgroup resident, one per CU), so the minimum changes the form only if the MOVE kernel fits no CU at all
+        int per_cu_mv = 0;
+        const void* fm = (const void*)rollout_kernel<lps, nt, p, true, true, false, true>;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_mv, fm, nt, 0) != hipSuccess) per_cu_mv = 0;
+        per_cu = std::min(per_cu, per_cu_mv);
     });
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + 2 * c->cfg.T, 0)) return rc;
     c->kc.acquire = c->hand.acquire;
@@ -1363,8 +1405,8 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
         double* prev = c->d_drows + c->drow * slab;
         double* mine = c->d_drows + (c->drow ^ 1) * slab;
         const unsigned fl = flags | (c->pending ? kFlagPending : 0u);
-        with_rollout(c, false, [&](auto lps, auto nt, auto p, auto cl, auto ob) {
-            hipLaunchKernelGGL((rollout_kernel<lps, nt, false, cl, ob, true>), dim3(c->nblocks), dim3(nt), 0, c->stream,
+        with_rollout(c, false, [&](auto lps, auto nt, auto p, auto cl, auto ob, auto mv) {
+            hipLaunchKernelGGL((rollout_kernel<lps, nt, false, cl, ob, true, mv>),dim3(c->nblocks), dim3(nt), 0, c->stream,
                                c->kc, c->stat, c->d_step + c->cur, nz, S_dev, mine, prev, nullptr, nullptr, c->d_weps,
                                c->d_step + (c->cur ^ 1), fl, c->ex.xd, nullptr, nullptr,
                                reinterpret_cast<float*>(c->d_upd.h), HostOut{nullptr, 0u}, c->d_dbg, c->ck, c->ok);
@@ -1383,8 +1425,8 @@ int launch_rollout(mppi_ctx* c, const float* noise_dev, double* S_dev, double* p
     flags &= ~MPPI_FLAG_INLINE_MERGE;
     const DevStep* cur = c->d_step + c->cur;
     DevStep* nxt = c->d_step + (c->cur ^ 1);
-    with_rollout(c, c->hand.poll, [&](auto lps, auto nt, auto p, auto cl, auto ob) {
-        hipLaunchKernelGGL((rollout_kernel<lps, nt, p, cl, ob>), dim3(c->nblocks), dim3(nt), 0, c->stream, c->kc, c->stat, cur,
+    with_rollout(c, c->hand.poll, [&](auto lps, auto nt, auto p, auto cl, auto ob, auto mv) {
+        hipLaunchKernelGGL((rollout_kernel<lps, nt, p, cl, ob, false, mv>),dim3(c->nblocks), dim3(nt), 0, c->stream, c->kc, c->stat, cur,
                            nz, S_dev, c->hand.d_slab, c->hand.d_gslab, c->hand.d_counter, partial_dev, c->d_weps, nxt,
                            flags, c->ex.xd, c->hand.d_epoch, c->hand.h_tmo.dev, reinterpret_cast<float*>(c->d_upd.h),
                            ho, c->d_dbg, c->ck, c->ok);
@@ -1683,6 +1725,10 @@ int mppi_debug_nearest(mppi_ctx* c, const float* noise_dev, int K, int* slot_dev
 }
 
 int mppi_set_obstacles(mppi_ctx* c, int n, const double* discs, double cost) {
+    return mppi_set_moving_obstacles(c, n, discs, nullptr, cost);
+}
+
+int mppi_set_moving_obstacles(mppi_ctx* c, int n, const double* discs, const double* vel, double cost) {
     if (!c) return fail(MPPI_E_ARG, "null context");
     if (n < 0 || n > MPPI_MAX_OBSTACLES) return fail(MPPI_E_ARG, "obstacles: n must be in [0, 8]");
     if (n > 0 && !discs) return fail(MPPI_E_ARG, "obstacles: null discs");
@@ -1696,7 +1742,18 @@ int mppi_set_obstacles(mppi_ctx* c, int n, const double* discs, double cost) {
         k.cx[j] = (float)cx;
         k.cy[j] = (float)cy;
         k.r2[j] = (float)(r * r);
+        if (!vel) continue;
+        const double vx = vel[2 * j], vy = vel[2 * j + 1];
+        if (!isfinite((float)vx) || !isfinite((float)vy)) return fail(MPPI_E_ARG, "obstacles: a velocity is not finite");
+        k.vx[j] = (float)vx;
+        k.vy[j] = (float)vy;
+        if (k.vx[j] != 0.f || k.vy[j] != 0.f) k.moving = 1;   // else the kernels of discs at rest, as vel = NULL
+        // the last row of the kernels' table (stage_obst_row at t = T - 1), the farthest the disc gets
+        const float tau = (float)((double)c->cfg.T * c->cfg.delta_t);
+        if (!isfinite(fmaf(k.vx[j], tau, k.cx[j])) || !isfinite(fmaf(k.vy[j], tau, k.cy[j])))
+            return fail(MPPI_E_ARG, "obstacles: a centre is not finite at the end of the horizon");
     }
+    k.dt = c->cfg.delta_t;
     k.w = cost;
     k.n = n;
     c->ok = k;   // read by the next launch of any kind (a kernel argument, by value): no device call

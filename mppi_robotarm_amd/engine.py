@@ -67,7 +67,10 @@ class _Engine:
                                        C.byref(ctx)), prefix + "ctx_create")
         self._ctx = ctx
         self.partial_len = 2 + self.dim_u * self.T
+        # (resolved leniently: the tools that time an older build of the library beside this one build engines on it)
+        self._c_set_moving_obstacles = getattr(self._lib, prefix + "set_moving_obstacles", None)
         self.obstacles, self.obstacle_cost = np.zeros((0, 3)), 0.0   # what set_obstacles last gave the context
+        self.obstacle_velocities = None                              # ... and its (n, 2) velocities, or None
 
     # -- torque limits ------------------------------------------------------
     @staticmethod
@@ -90,7 +93,7 @@ class _Engine:
         self.u_min = None if not cfg.clamp_mode else np.array(cfg.u_min[:dim_u])
         self.u_max = None if not cfg.clamp_mode else np.array(cfg.u_max[:dim_u])
 
-    # -- workspace obstacles (both ABIs: mppi_set_obstacles, mppi_chain_set_obstacles) --
+    # -- workspace obstacles (both ABIs: mppi_[chain_]set_obstacles, mppi_[chain_]set_moving_obstacles) --
     @staticmethod
     def check_obstacles(discs, cost) -> tuple[np.ndarray, float]:
         """(discs as a C-contiguous fp64 (n, 3) array of (cx, cy, r), cost as a float), or ValueError: at most
@@ -115,14 +118,45 @@ class _Engine:
             raise ValueError("obstacle_cost must be finite and >= 0")
         return np.ascontiguousarray(a), w
 
-    def set_obstacles(self, discs, cost: float = 1.0e10) -> None:
+    @staticmethod
+    def check_velocities(velocities, n: int) -> np.ndarray | None:
+        """velocities as a C-contiguous fp64 (n, 2) array of (vx, vy) in m/s, or None for None (every disc at
+        rest), or ValueError: velocities without discs, a shape other than (n, 2) for the n discs, an entry that
+        is not finite (in fp32, the kernels' format)."""
+        if velocities is None:
+            return None
+        try:
+            v = np.array(velocities, dtype=np.float64, ndmin=1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"obstacle_velocities: {e}") from None
+        if n == 0:
+            raise ValueError("obstacle_velocities given without obstacles")
+        if v.shape != (n, 2):
+            raise ValueError(f"obstacle_velocities must be ({n}, 2) rows of (vx, vy), one per disc, got shape {v.shape}")
+        with np.errstate(over="ignore"):
+            if not np.all(np.isfinite(v.astype(np.float32))):
+                raise ValueError("obstacle_velocities: a velocity is not finite")
+        return np.ascontiguousarray(v)
+
+    def set_obstacles(self, discs, cost: float = 1.0e10, velocities=None) -> None:
         """Discs (n, 3) of (cx, cy, r), n <= 8, that no link may touch, and the cost a colliding step adds
         to its sample's S (the final state once more): <prefix>set_obstacles.  In effect from the next launch of
-        any kind; None or no rows removes them.  No device call.  ValueError for a bad shape or value."""
+        any kind; None or no rows removes them.  No device call.  ValueError for a bad shape or value.
+
+        velocities: (n, 2) of (vx, vy) in m/s, constant over the horizon, or None for discs at rest
+        (mppi_set_moving_obstacles): `discs` holds the positions at the observed state, and the state that
+        rollout step t produces is tested against the centres at c + v (t + 1) delta_t."""
         a, w = self.check_obstacles(discs, cost)
-        N.check(self._c_set_obstacles(self._ctx, a.shape[0], _dptr(a) if a.shape[0] else None, w),
-                self._prefix + "set_obstacles")
-        self.obstacles, self.obstacle_cost = a, w
+        v = self.check_velocities(velocities, a.shape[0])
+        if v is None:
+            N.check(self._c_set_obstacles(self._ctx, a.shape[0], _dptr(a) if a.shape[0] else None, w),
+                    self._prefix + "set_obstacles")
+        else:
+            if self._c_set_moving_obstacles is None:
+                raise ValueError(f"{self._prefix}set_moving_obstacles: this build of the library has no moving obstacles")
+            N.check(self._c_set_moving_obstacles(self._ctx, a.shape[0], _dptr(a), _dptr(v), w),
+                    self._prefix + "set_moving_obstacles")
+        self.obstacles, self.obstacle_cost, self.obstacle_velocities = a, w, v
 
     # -- lifetime -----------------------------------------------------------
     def close(self) -> None:

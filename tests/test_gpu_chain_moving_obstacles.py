@@ -1,0 +1,384 @@
+"""GPU: moving obstacles for the n-link chain (mppi_chain_set_moving_obstacles; the MOVE instantiations of
+chain_rollout_kernel in its three forms: fp32 with one lane per sample, fp32 with a quad per sample, fp64).
+
+Yardstick: tests/moving_obstacle_ref.py (O.horizon_loop on chain_model with the discs at c + v (t + 1) dt), pinned to
+the arm's and to the reference's fixtures at n = 2 by test_chain_moving_obstacle_cpu.py.  Shapes, the shared problem
+of (n, K), EDGE(n) and the treatment of the flag's discontinuity are test_gpu_chain_obstacles.py's: masks against the
+fp64 predicate on the device's OWN directions, the penalty exactly through S = S_free + w hits with the device's own
+hit counts, the yardstick with the device's hit counts where a weight depends on them.  The bounds against the
+yardstick at n = 3 and 7 with non-uniform links (helpers.asym_chain_inputs) are the chain suite's: fp32 S p99 <= 2e-4,
+w_eps <= 1e-4, fp64 S <= 1e-11.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+import chain_oracle as CO  # noqa: E402
+import moving_obstacle_ref as MR  # noqa: E402
+import mppi_oracle as O  # noqa: E402
+from conftest import GOLDEN  # noqa: E402
+from helpers import _gpu, _urel, asym_chain_inputs  # noqa: E402, F401
+from test_gpu_chain_obstacles import (ALPHA, COSTS, DT, FORM_IDS, FORMS, NS, S_TOL, TW, U_TOL, W, T,  # noqa: E402
+                                      _bits, _chains, _engine, _hits_from_masks, _problem, _S, _sigma, _stage, edge,
+                                      place_discs)
+
+PAIR_CAP = 0.005            # at most 0.5 % of the (sample, step, link, disc) pairs may differ, all within EDGE
+MOVE_STEPS = ["a_k128_t20", "b_dense_k256_t24", "c_expl_k128_t20", "d_clamp_k128_t20"]
+
+
+def _arrive(discs):
+    """(discs, vel): each disc crosses its own radius over the horizon, in directions spread round the circle, and is
+    where the static layout has it at the END of the horizon; disc 5 stays at rest (a mixed table)."""
+    n = discs.shape[0]
+    ang = 2.0 * np.pi * np.arange(n) / 8.0 + 0.4
+    v = (discs[:, 2] / (T * DT))[:, None] * np.stack([np.cos(ang), np.sin(ang)], -1)
+    if n > 5:
+        v[5] = 0.0
+    d = discs.copy()
+    d[:, :2] -= v * (T * DT)
+    return d, v
+
+
+def _mref(n, K, paths, discs, vel, w, lam=100.0, shift=0, hits=None, step=False):
+    p = _problem(n, K, paths)
+    args = (p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW, 0.0, _chains(n)[1])
+    if step:
+        return MR.chain_moving_step(*args, discs=discs, vel=vel, obstacle_cost=w, hits=hits)
+    return MR.chain_moving_costs(*args, discs=discs, vel=vel, obstacle_cost=w, shift=shift)
+
+
+def _set_raw(eng, discs, vel, cost):
+    dp = C.POINTER(C.c_double)
+    a = np.ascontiguousarray(discs, dtype=np.float64)
+    v = None if vel is None else np.ascontiguousarray(vel, dtype=np.float64)
+    return eng._lib.mppi_chain_set_moving_obstacles(eng._ctx, a.shape[0], a.ctypes.data_as(dp),
+                                                    None if v is None else v.ctypes.data_as(dp), cost)
+
+
+def _compare_masks(mask, d, discs, vel, n, fk, E, what):
+    nd = discs.shape[0]
+    want, gap = MR.chain_moving_masks(d, discs, vel, DT, fk)
+    differ = ((mask[..., None, None] ^ want[..., None, None]) & _bits(nd, n)) != 0
+    worst = float(gap[differ].max()) if differ.any() else 0.0
+    print(f"{what}: {float(np.mean(mask != 0)):.1%} of the states collide, {int(differ.sum())} bits differ "
+          f"(largest clearance {worst:.2e} m, EDGE {E:.2e} m)")
+    assert not np.any(differ & (gap > E)), f"{what}: a bit differs at clearance {worst:.2e} m"
+    assert float(np.mean(differ)) <= PAIR_CAP
+    assert not np.any(mask & ~np.bitwise_or.reduce(_bits(nd, n).ravel()))
+    return want
+
+
+# ---------------------------------------------------------------- 1: at rest equals static
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_at_rest_is_the_static_feature_bit_for_bit(precision, lps, K, n, paths):
+    from mppi_robotarm_amd import _native as N
+    p = _problem(n, K, paths)
+    got = []
+    for how in ("static", "null", "zeros"):
+        eng = _engine(n, K, 3.0e6, precision, lps)
+        noise = _stage(eng, p, paths)
+        if how == "static":
+            eng.set_obstacles(p["discs"], 3.0e6)
+        elif how == "null":
+            assert _set_raw(eng, p["discs"], None, 3.0e6) == N.MPPI_OK
+        else:
+            eng.set_obstacles(p["discs"], 3.0e6, velocities=np.zeros((8, 2)))
+        S = _S(eng, noise, fused_update=True)
+        got.append((S, eng.weighted_noise(), eng.nominal(), eng.obstacle_hits(noise)[0]))
+        eng.close()
+    assert 0.10 <= float(np.mean(_hits_from_masks(got[0][3]) > 0)) <= 0.90
+    for other in got[1:]:
+        for a, b in zip(got[0], other):
+            assert np.array_equal(a, b)
+
+
+# ---------------------------------------------------------------- 2: masks on the device's own directions
+
+@pytest.mark.parametrize("nd", [1, 3, 8])
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_masks_on_the_devices_own_directions(precision, lps, K, n, nd, paths):
+    p = _problem(n, K, paths)
+    discs, vel = _arrive(p["discs"][:nd])
+    E = edge(n, p["discs"])
+    fk = _chains(n)[1].fk
+    # the inputs, by the fp64 yardstick alone: >= 99.5 % of the pairs lie outside EDGE, where no bit may differ
+    th = np.cumsum(p["free"]["q"], -1)
+    ref_mask, ref_gap = MR.chain_moving_masks(np.concatenate([np.cos(th), np.sin(th)], -1), discs, vel, DT, fk)
+    assert float(np.mean(ref_gap > E)) >= 0.995
+    r = _mref(n, K, paths, discs, vel, 0.0)
+    assert np.array_equal(ref_mask != 0, r["flag"])
+    rest = _mref(n, K, paths, discs, None, 0.0)
+    assert float(np.mean(r["hits"] != rest["hits"])) >= 0.10        # the motion matters on this problem
+    eng = _engine(n, K, precision=precision, lps=lps)
+    noise = _stage(eng, p, paths)
+    eng.set_obstacles(discs, 1.0e10, velocities=vel)
+    mask, d = eng.obstacle_hits(noise)
+    eng.close()
+    assert float(np.max(np.abs(d - np.concatenate([np.cos(th), np.sin(th)], -1)))) < 1e-4
+    _compare_masks(mask, d, discs, vel, n, fk, E, f"{precision} lps {lps} n {n} discs {nd}")
+    assert float(np.mean((mask != 0) == r["flag"])) >= 0.99
+
+
+# ---------------------------------------------------------------- 3: the time index
+
+_fast = {}
+
+
+def _fast_disc(n, K, paths):
+    """The most-touched disc of the shared layout, made fast: |v| dt = 3 r, and where the layout has it exactly at
+    T dt, so a step earlier it is three radii back along its line and a step later three radii on.  The line: the
+    first of 16 directions, starting with the one through the chain's median final tip, on which by the fp64 yardstick
+    alone 10-90 % of the samples collide (the disc crosses no other link on its way in) and either off-by-one
+    definition changes the flags of >= 10 % of the samples."""
+    if (n, K) not in _fast:
+        p = _problem(n, K, paths)
+        d0 = p["discs"][0]
+        th = np.cumsum(np.median(p["free"]["q"][:, -1], 0))
+        fk = np.asarray(_chains(n)[1].fk)
+        out = d0[:2] - np.array([(fk * np.cos(th)).sum(), (fk * np.sin(th)).sum()])
+        a0 = float(np.arctan2(out[1], out[0]))
+        for k in range(16):
+            v = -(3.0 * d0[2] / DT) * np.array([np.cos(a0 + k * np.pi / 8), np.sin(a0 + k * np.pi / 8)])
+            discs, vel = np.array([[d0[0] - v[0] * T * DT, d0[1] - v[1] * T * DT, d0[2]]]), v[None, :]
+            r = _mref(n, K, paths, discs, vel, 0.0)
+            if not 0.10 <= float(np.mean(r["flag"].any(1))) <= 0.90:
+                continue
+            if all(float(np.mean((_mref(n, K, paths, discs, vel, 0.0, shift=sh)["flag"] != r["flag"]).any(1))) >= 0.10
+                   for sh in (-1, 1)):
+                _fast[(n, K)] = (discs, vel, r)
+                break
+    return _fast[(n, K)]
+
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_time_index(precision, lps, K, n, paths):
+    p = _problem(n, K, paths)
+    discs, vel, r = _fast_disc(n, K, paths)   # (asserts the CPU side: 10-90 % collide, >= 10 % differ a step off)
+    assert float(np.linalg.norm(vel[0])) * DT > 2.0 * discs[0, 2]
+    w = 7.0
+    eng = _engine(n, K, precision=precision, lps=lps)
+    noise = _stage(eng, p, paths)
+    S_free = _S(eng, noise)
+    eng.set_obstacles(discs, w, velocities=vel)
+    mask, d = eng.obstacle_hits(noise)
+    S = _S(eng, noise)
+    eng.close()
+    fk = _chains(n)[1].fk
+    E = (6 + 2 * n) * 2.0 ** -24 * (float(np.hypot(*discs[0, :2])) + 2.0)   # edge(): this disc starts further out
+    _compare_masks(mask, d, discs, vel, n, fk, E, f"{precision} lps {lps} n {n} fast")
+    for shift in (-1, 1):
+        off, _ = MR.chain_moving_masks(d, discs, vel, DT, fk, shift=shift)
+        assert float(np.mean((off != mask).any(1))) >= 0.10, shift
+    hits = _hits_from_masks(mask)
+    assert np.array_equal(S, S_free + w * hits.astype(np.float64))      # the final state counted with step T - 1's
+    assert (mask[:, -1] != 0).any()
+
+
+# ---------------------------------------------------------------- 4: the decomposition, bit for bit
+
+@pytest.mark.parametrize("handoff", ["poll", "counter"])
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_S_is_the_no_disc_S_plus_w_hits_bit_for_bit(precision, lps, K, n, handoff, paths, monkeypatch):
+    if handoff == "counter":
+        monkeypatch.setenv("MPPI_HANDOFF", "counter")
+    else:
+        monkeypatch.delenv("MPPI_HANDOFF", raising=False)
+    p = _problem(n, K, paths)
+    eng = _engine(n, K, 3.0e6, precision, lps)
+    assert eng.handoff == handoff
+    noise = _stage(eng, p, paths)
+    S_free, weps_free = _S(eng, noise), eng.weighted_noise()
+    for nd, w in COSTS:
+        discs, vel = _arrive(p["discs"][:nd])
+        eng.set_obstacles(discs, w, velocities=vel)
+        S = _S(eng, noise)
+        hits = _hits_from_masks(eng.obstacle_hits(noise)[0])
+        assert hits.max() <= T + 1 and hits.max() > 0
+        assert np.array_equal(S, S_free + w * hits.astype(np.float64)), (nd, w)
+    eng.set_obstacles(None, 1.0e10)                            # n = 0 after moving discs: no trace
+    assert np.array_equal(_S(eng, noise), S_free) and np.array_equal(eng.weighted_noise(), weps_free)
+    eng.close()
+
+
+# ---------------------------------------------------------------- 7: against the yardstick, non-uniform links
+
+_asym = {}
+
+
+def _asym_problem(n, K, paths):
+    """A non-uniform chain (helpers.asym_chain_inputs), host noise in fp32, the unobstructed yardstick run and discs
+    placed from it (place_discs), made to move (_arrive): computed once per (n, K) and shared."""
+    if (n, K) not in _asym:
+        import mppi_robotarm_amd.chain as chain_mod
+        P, x0, sig, u = asym_chain_inputs(n, T, chain_mod)
+        Po = asym_chain_inputs(n, T, CO)[0]
+        rng = np.random.default_rng(300 * n + K)
+        eps = (rng.normal(size=(K, T, n)) @ np.linalg.cholesky(sig).T).astype(np.float32).astype(np.float64)
+        args = (x0, u, eps, paths["xydq_circle"], 40, DT, 3.0e6, ALPHA, sig, W, TW, 0.0, Po)
+        free = MR.chain_moving_costs(*args)
+        discs, vel = _arrive(place_discs(free, Po))
+        _asym[(n, K)] = dict(P=P, Po=Po, x0=x0, sig=sig, u=u, eps=eps, args=args, discs=discs, vel=vel)
+    return _asym[(n, K)]
+
+
+@pytest.mark.parametrize("n", [3, 7])
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_non_uniform_chain_against_the_yardstick(precision, lps, K, n, paths):
+    from mppi_robotarm_amd.chain import ChainEngine
+    a = _asym_problem(n, K, paths)
+    lam, w = 3.0e6, 3.0e6
+    eng = ChainEngine(K, T, DT, lam, ALPHA, a["sig"], W, TW, 0.0, a["P"], device=0, precision=precision,
+                      lanes_per_sample=lps)
+    eng.set_step_inputs(a["x0"], paths["xydq_circle"][40:70], a["u"])
+    noise = eng.upload_noise(a["eps"])
+    eng.set_obstacles(a["discs"], w, velocities=a["vel"])
+    S, weps = _S(eng, noise), eng.weighted_noise()
+    hits = _hits_from_masks(eng.obstacle_hits(noise)[0])
+    eng.close()
+    r = MR.chain_moving_step(*a["args"], discs=a["discs"], vel=a["vel"], obstacle_cost=w, hits=hits)
+    assert 0.10 <= float(np.mean(r["flag"].any(1))) <= 0.90
+    assert float(np.mean(hits == r["hits"])) >= 0.99
+    rel = np.abs(S - r["S"]) / np.abs(r["S"])
+    print(f"{precision} lps {lps} n {n}: S rel p99 {float(np.percentile(rel, 99)):.2e} max {float(rel.max()):.2e}, "
+          f"w_eps {_urel(weps, r['w_eps_raw']):.2e}")
+    if precision == "f64":
+        assert float(rel.max()) <= 1e-11
+    else:
+        assert float(np.percentile(rel, 99)) <= 2e-4
+    assert _urel(weps, r["w_eps_raw"]) <= 1e-4
+
+
+# ---------------------------------------------------------------- 7: n = 2 against the reference's fixtures
+
+def _load(name):
+    return dict(np.load(os.path.join(GOLDEN, f"move_step_{name}.npz")))
+
+
+def _n2_controller(g, paths, precision, **kw):
+    from mppi_robotarm_amd.chain import ChainMPPIController, ChainParams
+    lim = dict(u_min=g["u_min"], u_max=g["u_max"]) if "u_min" in g else {}
+    c = ChainMPPIController(float(g["delta_t"]), paths[str(g["path"])], int(g["T"]), int(g["K"]),
+                            float(g["param_exploration"]), float(g["param_lambda"]), float(g["param_alpha"]),
+                            g["sigma"], g["stage_cost_weight"], g["terminal_cost_weight"],
+                            visualize_optimal_traj=bool(g["visualize_optimal_traj"]), chain=ChainParams.from_arm2(),
+                            u_init=g["u_prev"], obstacles=g["obstacles"], obstacle_cost=float(g["obstacle_cost"]),
+                            obstacle_velocities=g["obstacle_velocities"], precision=precision, **lim, **kw)
+    c.prev_waypoints_idx = int(g["prev_idx"])
+    return c
+
+
+@pytest.mark.parametrize("precision", ["f32", "f64"])
+@pytest.mark.parametrize("name", MOVE_STEPS)
+def test_chain_at_n2_reproduces_the_moving_reference_steps(name, precision, paths):
+    g = _load(name)
+    c = _n2_controller(g, paths, precision)
+    eps = g["eps"].astype(np.float64)
+    c._calc_epsilon = lambda *a, **k: eps
+    c.keep_costs = True
+    u0, u_seq, opt, _ = c.calc_control_input(g["x0"])
+    S = c.last_S
+    assert c.last_precision == precision
+    assert np.array_equal(c._engine.obstacle_velocities, g["obstacle_velocities"])
+    clean = g["clearance"].min(1) >= 1e-4
+    assert float(np.mean(clean)) >= 0.80
+    rel = float(np.max(np.abs(S[clean] - g["S"][clean]) / np.abs(g["S"][clean])))
+    print(f"{name} {precision}: S rel {rel:.2e} on {int(clean.sum())}/{clean.size} samples")
+    assert rel < S_TOL
+    assert c.prev_waypoints_idx == int(g["prev_idx_after"])
+    w = float(g["obstacle_cost"])
+    r = MR.chain_moving_costs(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]),
+                              float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
+                              g["stage_cost_weight"], g["terminal_cost_weight"], float(g["param_exploration"]),
+                              CO.ChainParams.from_arm2(), lo=g.get("u_min"), hi=g.get("u_max"), discs=g["obstacles"],
+                              vel=g["obstacle_velocities"], obstacle_cost=w)
+    hits = np.rint((S - r["S_track"]) / w)
+    assert float(np.mean(hits == r["hits"])) >= 0.99
+    assert float(np.mean(hits != g["hits_rest"])) >= 0.50      # not the static feature
+    if bool(g["one_hot"]):
+        assert int(np.argmin(S)) == int(np.argmin(g["S"]))
+        assert _urel(u_seq, g["u_seq"]) < U_TOL and _urel(u0, g["u0"]) < U_TOL
+    else:
+        up = O.update(r["S_track"] + w * hits, g["u_prev"], eps, float(g["param_lambda"]), g["x0"],
+                      float(g["delta_t"]), g.get("u_min"), g.get("u_max"))
+        assert _urel(u_seq, up["u_seq"]) < U_TOL
+    c.close()
+
+
+def test_auto_precision_carries_the_velocities_into_its_fp64_engine(paths):
+    """precision="auto" on the dense-weight fixture: the fp32 step's weights are spread, so the same call runs the
+    step again on the fp64 engine, which it builds with this call's discs AND velocities; an in-place edit of the
+    velocities reaches both engines on the next call.  On the one-hot fixture the call stays on the fp32 engine."""
+    g = _load("b_dense_k256_t24")
+    eps = g["eps"].astype(np.float64)
+    vel = g["obstacle_velocities"].copy()
+    c = _n2_controller(g, paths, "auto")
+    c.obstacle_velocities = vel
+    c.keep_costs = True
+    c._calc_epsilon = lambda *a, **k: eps
+
+    def call():
+        c.u_prev[:] = g["u_prev"]
+        c.prev_waypoints_idx = int(g["prev_idx"])
+        c._spread = False
+        c.calc_control_input(g["x0"])
+        return c.last_S.copy()
+
+    S = call()
+    assert c.last_precision == "f64" and c._active == "f64" and "f32" in c._slots    # both engines ran this call
+    clean = g["clearance"].min(1) >= 1e-4
+    assert float(np.max(np.abs(S[clean] - g["S"][clean]) / np.abs(g["S"][clean]))) < S_TOL
+    for eng in (c._engine, c._slots["f32"]["_engine"]):
+        assert np.array_equal(eng.obstacle_velocities, vel) and np.array_equal(eng.obstacles, g["obstacles"])
+    vel[2] = 0.0                 # in place: the disc ahead of the end effector stops (by the yardstick, 81 % of
+                                 # the samples' hit counts change; the first disc's velocity changes none here)
+    S2 = call()
+    assert c.last_precision == "f64" and not np.array_equal(S2, S)
+    for eng in (c._engine, c._slots["f32"]["_engine"]):
+        assert np.array_equal(eng.obstacle_velocities, vel)
+    c.obstacle_velocities = [[0.0, float("nan")]] * 4
+    with pytest.raises(ValueError):
+        c.calc_control_input(g["x0"])
+    c.close()
+    g = _load("a_k128_t20")                                    # one sample carries the weight: no second engine
+    c = _n2_controller(g, paths, "auto")
+    eps1 = g["eps"].astype(np.float64)
+    c._calc_epsilon = lambda *a, **k: eps1
+    c.keep_costs = True
+    c.calc_control_input(g["x0"])
+    assert c.last_precision == "f32" and not c._slots
+    assert int(np.argmin(c.last_S)) == int(np.argmin(g["S"]))
+    c.close()
+
+
+def test_set_moving_obstacles_rejects_bad_arguments(paths):
+    from mppi_robotarm_amd import _native as N
+    n, K = 3, 300
+    p = _problem(n, K, paths)
+    discs, vel = _arrive(p["discs"][:2])
+    eng = _engine(n, K)
+    noise = _stage(eng, p, paths)
+    eng.set_obstacles(discs, 1.0e10, velocities=vel)
+    S = _S(eng, noise)
+    nan, inf = float("nan"), float("inf")
+    ok_d, ok_v = [[0.0, 0.0, 0.1]], [[0.1, 0.0]]
+    for d, v, cost in ((ok_d, [[nan, 0.0]], 1.0), (ok_d, [[0.0, inf]], 1.0), (ok_d, [[1e300, 0.0]], 1.0),
+                       ([[3.3e38, 0.0, 0.1]], [[3.0e38, 0.0]], 1.0),      # both finite, the centre at T dt is not
+                       ([[0.0, 0.0, -0.1]], ok_v, 1.0), (ok_d, ok_v, -1.0), (ok_d, ok_v, nan)):
+        assert _set_raw(eng, d, v, cost) == N.MPPI_E_ARG, (d, v, cost)
+        assert b"obstacles" in eng._lib.mppi_last_error()
+    assert eng._lib.mppi_chain_set_moving_obstacles(eng._ctx, 1, None, None, 1.0) == N.MPPI_E_ARG
+    for bad in ([[0.1, 0.0]], [[0.1, nan], [0.0, 0.0]], np.zeros((2, 3))):
+        with pytest.raises(ValueError):
+            eng.set_obstacles(discs, 1.0, velocities=bad)
+    assert np.array_equal(_S(eng, noise), S)                    # a rejected call keeps discs and velocities in effect
+    eng.close()
