@@ -37,6 +37,12 @@ reference's 4-term weighted squared error x 10000 on (x, y, dq_1, dq_2) against
 xydq_circle.txt's (x, y, dq1, dq2) columns; control cost (gamma u_t^T Sigma^-1) v
 (control.py:106) with the n x n Sigma; weights / weighted noise / median filter /
 update / shift exactly as the 2-DoF step (control.py:112-152).
+
+Workspace obstacles (discs, at rest or moving): the arm's collision cost
+(O.collision_costs) with every link of the chain tested (chain_collides); a
+state collides when any link touches any disc.  At n = 2 with
+ChainParams.from_arm2() it is the arm's definition (test_chain_obstacle_cpu.py,
+test_chain_moving_obstacle_cpu.py).
 """
 from __future__ import annotations
 
@@ -138,35 +144,89 @@ def chain_state_cost(q, dq, ref_path, prev_idx, weight, P: ChainParams):
     return c * 10000
 
 
+def chain_segment_test(c, s, discs, fk):
+    """Every link against every disc from the direction values c, s (..., n): (dist (..., nd, n) fp64, the distance
+    from disc j's centre to link a with the projection clipped to the segment; clipped (..., nd, n) int8, -1 / +1
+    where the projection was clipped to the link's base / tip, 0 where it is interior).
+
+    Link a (0-based) is the zero-thickness segment from b_{a-1} to b_a, b_a = sum_{i <= a} fk_i (cos th_i, sin th_i)
+    with b_{-1} the origin, th the absolute angles and fk the cost's link lengths (chain_fk's).  At n = 2 with
+    ChainParams.from_arm2() this is O.segment_test (test_chain_obstacle_cpu.py)."""
+    d = np.asarray(discs, dtype=np.float64).reshape(-1, 3)
+    c, s = np.asarray(c, dtype=np.float64), np.asarray(s, dtype=np.float64)
+    fk = np.asarray(fk, dtype=np.float64)
+    bx = np.cumsum(fk * c, -1) - fk * c            # base of link a: b_{a-1}
+    by = np.cumsum(fk * s, -1) - fk * s
+    px = d[:, 0][:, None] - bx[..., None, :]       # (..., nd, n)
+    py = d[:, 1][:, None] - by[..., None, :]
+    ux, uy = c[..., None, :], s[..., None, :]
+    pr = px * ux + py * uy
+    t = np.clip(pr, 0.0, fk)
+    dist = np.hypot(px - t * ux, py - t * uy)
+    clipped = np.where(pr < 0.0, -1, np.where(pr > fk, 1, 0)).astype(np.int8)
+    return dist, clipped
+
+
+def chain_touch_mask(dist, discs):
+    """The masks of mppi_chain_debug_obstacle_hits from chain_segment_test's distances: bit 8 j + a is link a
+    touching disc j (uint64, dist's shape without its last two axes)."""
+    r = np.asarray(discs, dtype=np.float64).reshape(-1, 3)[:, 2]
+    hit = dist < r[:, None]
+    nd, n = hit.shape[-2:]
+    bits = np.uint64(1) << (np.uint64(8) * np.arange(nd, dtype=np.uint64)[:, None] + np.arange(n, dtype=np.uint64))
+    return np.bitwise_or.reduce(np.where(hit, bits, np.uint64(0)).reshape(hit.shape[:-2] + (-1,)), axis=-1) \
+        if nd else np.zeros(hit.shape[:-2], dtype=np.uint64)
+
+
+def chain_collides(q, discs, P):
+    """(flag, clearance, dist, clipped) of the states q (..., n) against the discs: flag where any link touches any
+    disc (its distance to the centre ``< r``), clearance |dist - r| of the nearest boundary (inf without discs)."""
+    th = np.cumsum(np.asarray(q, dtype=np.float64), -1)
+    dist, clipped = chain_segment_test(np.cos(th), np.sin(th), discs, P.fk)
+    r = np.asarray(discs, dtype=np.float64).reshape(-1, 3)[:, 2]
+    flag = np.any(dist < r[:, None], axis=(-1, -2))
+    return flag, O.clearance(dist, discs), dist, clipped
+
+
+def chain_moving_masks(dirs, discs, vel, dt, fk, shift=0):
+    """O.masks_over_horizon for the chain, dirs (K, T, 2 n) = (cos th_a at a, sin th_a at n + a): mask uint64 as
+    mppi_chain_debug_obstacle_hits lays it out, gap (K, T, nd, n)."""
+    n = np.shape(dirs)[-1] // 2
+    return O.masks_over_horizon(lambda a, d: chain_segment_test(a[:, :n], a[:, n:], d, fk)[0], chain_touch_mask,
+                                dirs, discs, vel, dt, shift)
+
+
 def chain_model(P: ChainParams = ChainParams()):
-    """The chain for mppi_oracle's horizon loop and update tail (O.Model); the state is (q, dq), each (K, n)."""
+    """The chain for mppi_oracle's horizon loop, collision cost and update tail (O.Model); the state is (q, dq),
+    each (K, n)."""
     n = P.n
     return O.Model(start=lambda x0, K: (np.tile(np.asarray(x0[:n], dtype=np.float64), (K, 1)),
                                         np.tile(np.asarray(x0[n:], dtype=np.float64), (K, 1))),
                    step=lambda s, v, dt: chain_forward_dynamics(*s, v, dt, P),
                    cost=lambda s, ref_path, prev_idx, weight: chain_state_cost(*s, ref_path, prev_idx, weight, P),
                    dot=lambda a, v: v @ a,
-                   trajectory=lambda x0, controls, dt: chain_rollout_trajectory(x0, controls, dt, P))
+                   trajectory=lambda x0, controls, dt: chain_rollout_trajectory(x0, controls, dt, P),
+                   collides=lambda s, discs: chain_collides(s[0], discs, P),
+                   record=lambda s: (np.stack(chain_fk(s[0], P), -1), s[0], s[1]))
 
 
 def chain_rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
                         expl=0.0, P: ChainParams = ChainParams(), k_offset=0, K_total=None, *, gamma=None,
-                        lo=None, hi=None):
-    """The K x T loop (control.py:81-109 with the chain model, O.horizon_loop).  eps (K, T, n); returns S (K,).
-    ``lo`` / ``hi``: torque limits, a scalar or per joint (the four rules of O.sampled_controls, per joint)."""
-    return O.horizon_loop(chain_model(P), x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
-                          expl, k_offset, K_total, gamma, lo, hi)[0]
+                        lo=None, hi=None, **kw):
+    """O.collision_costs for the chain: the K x T loop (control.py:81-109 with the chain model).  eps (K, T, n);
+    returns S (K,), or with ``details=True`` the dict, dist and clipped (K, T, nd, n) of chain_segment_test.
+    ``lo`` / ``hi``: torque limits, a scalar or per joint (the four rules of O.sampled_controls, per joint);
+    ``discs``, ``vel``, ``obstacle_cost``, ``shift``: the collision cost, as O.rollout_costs'."""
+    return O.collision_costs(chain_model(P), x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
+                             expl, k_offset, K_total, gamma, lo, hi, **kw)
 
 
 def step(x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
-         P: ChainParams = ChainParams(), *, gamma=None, lo=None, hi=None, visualize_optimal_traj=True, sampled=False):
-    """One calc_control_input after its waypoint update, with limits when given; ``prev_idx`` is the updated
-    index.  Returns S joined with O.update_in_place's dict."""
-    u = np.array(u_prev, dtype=np.float64)
-    S = chain_rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl, P,
-                            gamma=gamma, lo=lo, hi=hi)
-    return dict(S=S, **O.update_in_place(chain_model(P), S, u, eps, lam, x0, dt, lo, hi, expl,
-                                         visualize_optimal_traj, sampled))
+         P: ChainParams = ChainParams(), **kw):
+    """O.model_step for the chain, with its keywords: gamma, lo, hi, discs, vel, obstacle_cost, hits,
+    visualize_optimal_traj, sampled."""
+    return O.model_step(chain_model(P), x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
+                        expl, **kw)
 
 
 def chain_rollout_trajectory(x0, controls, dt, P: ChainParams = ChainParams()):

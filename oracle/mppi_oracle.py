@@ -13,9 +13,11 @@ torque limits (``lo`` / ``hi``: the reference's clamp hook ``_g`` switched on)
 and with workspace obstacles (``discs``: a collision cost inside ``_c`` and
 ``_phi``), are pinned by ``tests/test_clamp_cpu.py`` and
 ``tests/test_obstacle_cpu.py`` to fixtures captured from the reference with
-only those hooks overridden.  There is ONE horizon loop (``horizon_loop``) and
+only those hooks overridden; discs that move (``vel``) by
+``tests/test_moving_obstacle_cpu.py``.  There is ONE horizon loop
+(``horizon_loop``), ONE collision-cost loop around it (``collision_costs``) and
 ONE update tail (``update_in_place``); the chain (``chain_oracle.py``) runs the
-same two with its own model.
+same three with its own model.
 
 Every function cites the reference line it restates.  Quirks kept on purpose
 (SURVEY §3.3): the returned ``u0`` is the post-shift row, ``u_seq`` aliases
@@ -191,17 +193,26 @@ def _controls(u, eps, exploit, lim):
 
 # What the one horizon loop and the one update tail need of a model (the chain's is chain_oracle.chain_model):
 # start(x0, K) -> state, step(state, v, dt) -> state, cost(state, ref_path, prev_idx, weight) -> (K,),
-# dot(a, v) -> (K,) the control cost a . v in the model's own expression (its bits are pinned), and
-# trajectory(x0, controls, dt) -> states.
-Model = namedtuple("Model", "start step cost dot trajectory")
+# dot(a, v) -> (K,) the control cost a . v in the model's own expression (its bits are pinned),
+# trajectory(x0, controls, dt) -> states, and for the collision cost (collision_costs):
+# collides(state, discs) -> (flag, clear, dist, clipped), the model's collision test, and
+# record(state) -> (ee (K, 2), q (K, n), dq (K, n)), what a state records per step.
+Model = namedtuple("Model", "start step cost dot trajectory collides record")
 
 
 def arm_model(p: ArmParams = ArmParams()):
+    def record(s):
+        q1, q2, dq1, dq2 = s
+        return (np.stack([p.fk_l1 * np.cos(q1) + p.fk_l2 * np.cos(q1 + q2),
+                          p.fk_l1 * np.sin(q1) + p.fk_l2 * np.sin(q1 + q2)], -1),
+                np.stack([q1, q2], -1), np.stack([dq1, dq2], -1))
+
     return Model(start=lambda x0, K: tuple(np.full(K, float(x0[i])) for i in range(4)),
                  step=lambda s, v, dt: forward_dynamics(*s, v[:, 0], v[:, 1], dt, p),
                  cost=lambda s, ref_path, prev_idx, weight: state_cost(*s, ref_path, prev_idx, weight, p),
                  dot=lambda a, v: a[0] * v[:, 0] + a[1] * v[:, 1],
-                 trajectory=lambda x0, controls, dt: rollout_trajectory(x0, controls, dt, p))
+                 trajectory=lambda x0, controls, dt: rollout_trajectory(x0, controls, dt, p),
+                 collides=lambda s, discs: collides(s[0], s[1], discs, p), record=record)
 
 
 def horizon_loop(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
@@ -236,44 +247,61 @@ def horizon_loop(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, s
     return S + phi, S_track
 
 
-def rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
-                  expl=0.0, p: ArmParams = ArmParams(), k_offset=0, K_total=None, gamma=None, *,
-                  lo=None, hi=None, discs=None, obstacle_cost=0.0, details=False):
-    """S (K,) fp64 of the arm's K x T loop (horizon_loop), optionally with torque limits ``lo`` / ``hi`` (a
-    scalar or per joint; sampled_controls has the clamp's rules) and the collision cost on ``discs``.
+def discs_at(discs, vel, t, dt, shift=0):
+    """The discs (n, 3) as rollout step t's new state meets them.  A disc is (cx, cy, r) plus, in ``vel``, a
+    velocity (vx, vy) in m/s, constant over the horizon of one call; the position given is the one at the observed
+    state x0.  Step t (0-based) produces the state at time (t + 1) dt, so it meets the centres
+    c + v (t + 1 + shift) dt, radii kept; ``vel=None`` is the discs at rest.  ``shift`` moves the evaluation time by
+    whole steps (shift = -1 is the off-by-one definition c + v t dt that the tests tell the device apart from)."""
+    d = np.array(np.zeros((0, 3)) if discs is None else discs, dtype=np.float64).reshape(-1, 3)
+    if vel is not None and d.shape[0]:
+        v = np.asarray(vel, dtype=np.float64).reshape(-1, 2)
+        assert v.shape[0] == d.shape[0]
+        tau = (t + 1 + shift) * dt
+        d[:, 0] = d[:, 0] + v[:, 0] * tau
+        d[:, 1] = d[:, 1] + v[:, 1] * tau
+    return d
+
+
+def collision_costs(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
+                    k_offset=0, K_total=None, gamma=None, lo=None, hi=None, *, discs=None, vel=None,
+                    obstacle_cost=0.0, shift=0, details=False):
+    """S (K,) fp64 of either model's K x T loop (horizon_loop) with the collision cost on ``discs``, which move
+    with ``vel`` (discs_at).
 
     The collision cost is the reference with ONLY ``_c`` and ``_phi`` (control.py:174-198) overridden to return
     ``... + obstacle_cost * collides(x)``, the penalty added after the x 10000: every step of the horizon whose
-    new state collides adds it to its sample's cost and the final state adds it once more, so
-    ``S = S_track + obstacle_cost * hits`` with ``hits`` in ``[0, T + 1]``.
+    new state collides adds it to its sample's cost and the final state adds it once more (against the centres of
+    the last step, so it repeats that step's flag): ``S = S_track + obstacle_cost * hits``, ``hits`` in
+    ``[0, T + 1]``.
 
     ``details=True`` returns a dict instead: S, S_track (K,) (the same loop without the penalty), flag (K, T)
-    bool per step's new state, clear (K, T) clearance, hits (K,) = flag.sum(1) + flag[:, -1], dist (K, T, n, 2),
-    clipped (K, T, n, 2), ee (K, T, 2) end effector, q (K, T, 2) joint angles, dq (K, T, 2) joint rates.
-    Without discs and without details the loop does no collision or bookkeeping work."""
-    rec, penalty = None, None
+    bool per step's new state, clear (K, T) clearance, hits (K,) = flag.sum(1) + flag[:, -1], dist and clipped
+    (K, T) + whatever model.collides returns per state, ee (K, T, 2) end effector, q and dq (K, T, n) joint angles
+    and rates.  Without discs and without details the loop does no collision or bookkeeping work."""
+    steps, penalty = [], None
     if discs is not None or details:
-        K, T, _ = eps.shape
-        discs = np.asarray(np.zeros((0, 3)) if discs is None else discs, dtype=np.float64).reshape(-1, 3)
-        n = discs.shape[0]
-        rec = dict(flag=np.zeros((K, T), dtype=bool), clear=np.zeros((K, T)), dist=np.zeros((K, T, n, 2)),
-                   clipped=np.zeros((K, T, n, 2), dtype=bool), ee=np.zeros((K, T, 2)), q=np.zeros((K, T, 2)),
-                   dq=np.zeros((K, T, 2)))
-
         def penalty(t, state):
-            q1, q2, dq1, dq2 = state
-            rec["flag"][:, t], rec["clear"][:, t], rec["dist"][:, t], rec["clipped"][:, t] = collides(q1, q2, discs, p)
-            rec["ee"][:, t, 0] = p.fk_l1 * np.cos(q1) + p.fk_l2 * np.cos(q1 + q2)
-            rec["ee"][:, t, 1] = p.fk_l1 * np.sin(q1) + p.fk_l2 * np.sin(q1 + q2)
-            rec["q"][:, t, 0], rec["q"][:, t, 1] = q1, q2
-            rec["dq"][:, t, 0], rec["dq"][:, t, 1] = dq1, dq2
-            return obstacle_cost * rec["flag"][:, t]
+            steps.append(model.collides(state, discs_at(discs, vel, t, dt, shift)) + model.record(state))
+            return obstacle_cost * steps[-1][0]
 
-    S, S_track = horizon_loop(arm_model(p), x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
-                              expl, k_offset, K_total, gamma, lo, hi, penalty)
+    S, S_track = horizon_loop(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl,
+                              k_offset, K_total, gamma, lo, hi, penalty)
     if not details:
         return S
+    rec = {k: np.stack(a, 1) for k, a in zip(("flag", "clear", "dist", "clipped", "ee", "q", "dq"), zip(*steps))}
     return dict(S=S, S_track=S_track, hits=rec["flag"].sum(1) + rec["flag"][:, -1], **rec)
+
+
+def rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
+                  expl=0.0, p: ArmParams = ArmParams(), k_offset=0, K_total=None, gamma=None, *,
+                  lo=None, hi=None, discs=None, vel=None, obstacle_cost=0.0, shift=0, details=False):
+    """collision_costs for the arm: S (K,) fp64 of its K x T loop, optionally with torque limits ``lo`` / ``hi`` (a
+    scalar or per joint; sampled_controls has the clamp's rules) and the collision cost on ``discs`` moving with
+    ``vel``; ``details=True`` returns collision_costs' dict, dist and clipped (K, T, n, 2) of segment_test."""
+    return collision_costs(arm_model(p), x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl,
+                           k_offset, K_total, gamma, lo, hi, discs=discs, vel=vel, obstacle_cost=obstacle_cost,
+                           shift=shift, details=details)
 
 
 def segment_test(c1, s1, c12, s12, discs, fk1=1.0, fk2=1.0):
@@ -321,6 +349,26 @@ def collides(q1, q2, discs, p: ArmParams = ArmParams()):
     r = np.asarray(discs, dtype=np.float64).reshape(-1, 3)[:, 2]
     flag = np.any(dist < r[:, None], axis=(-1, -2))
     return flag, clearance(dist, discs), dist, clipped
+
+
+def masks_over_horizon(segments, touch, dirs, discs, vel, dt, shift=0):
+    """The fp64 predicate on recorded direction values dirs (K, T, ...), step t against discs_at(t): (mask (K, T)
+    of ``touch(dist, discs)``, gap (K, T) + dist's = |dist - r|), dist from ``segments(dirs[:, t], discs)``."""
+    dirs = np.asarray(dirs, dtype=np.float64)
+    mask, gap = [], []
+    for t in range(dirs.shape[1]):
+        d = discs_at(discs, vel, t, dt, shift)
+        dist = segments(dirs[:, t], d)
+        mask.append(touch(dist, d))
+        gap.append(np.abs(dist - d[:, 2][:, None]))
+    return np.stack(mask, 1), np.stack(gap, 1)
+
+
+def moving_masks(dirs, discs, vel, dt, fk1=1.0, fk2=1.0, shift=0):
+    """masks_over_horizon for the arm, dirs (K, T, 4) = (c1, s1, c12, s12): mask uint32 as
+    mppi_debug_obstacle_hits lays it out, gap (K, T, n, 2)."""
+    return masks_over_horizon(lambda a, d: segment_test(a[:, 0], a[:, 1], a[:, 2], a[:, 3], d, fk1, fk2)[0],
+                              touch_mask, dirs, discs, vel, dt, shift)
 
 
 def compute_weights(S, lam):
@@ -424,17 +472,28 @@ def update(S, u_prev, eps, lam, x0, dt, lo=None, hi=None, visualize_optimal_traj
                            visualize_optimal_traj)
 
 
-def step(x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
-         p: ArmParams = ArmParams(), gamma=None, *, lo=None, hi=None, discs=None, obstacle_cost=0.0,
-         visualize_optimal_traj=True, sampled=False):
-    """One calc_control_input after its waypoint update (control.py:81-152), with limits and discs when given;
-    ``prev_idx`` is the updated index.  rollout_costs(details=True)'s dict joined with update_in_place's."""
+def model_step(model, x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
+               gamma=None, *, lo=None, hi=None, discs=None, vel=None, obstacle_cost=0.0, hits=None,
+               visualize_optimal_traj=True, sampled=False):
+    """One calc_control_input of either model after its waypoint update (control.py:81-152), with limits and
+    (moving) discs when given; ``prev_idx`` is the updated index.  collision_costs(details=True)'s dict joined with
+    update_in_place's.  ``hits`` (K,), when given, replaces the yardstick's own hit counts in S (the device's: a
+    state within rounding of a boundary may fall on either side, and must not move a weight)."""
     u = np.array(u_prev, dtype=np.float64)
-    out = rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl, p, gamma=gamma,
-                        lo=lo, hi=hi, discs=discs, obstacle_cost=obstacle_cost, details=True)
-    out.update(update_in_place(arm_model(p), out["S"], u, eps, lam, x0, dt, lo, hi, expl, visualize_optimal_traj,
-                               sampled))
+    out = collision_costs(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl,
+                          gamma=gamma, lo=lo, hi=hi, discs=discs, vel=vel, obstacle_cost=obstacle_cost, details=True)
+    if hits is not None:
+        out["S"] = out["S_track"] + obstacle_cost * np.asarray(hits, dtype=np.float64)
+    out.update(update_in_place(model, out["S"], u, eps, lam, x0, dt, lo, hi, expl, visualize_optimal_traj, sampled))
     return out
+
+
+def step(x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
+         p: ArmParams = ArmParams(), gamma=None, **kw):
+    """model_step for the arm, with its keywords: lo, hi, discs, vel, obstacle_cost, hits, visualize_optimal_traj,
+    sampled."""
+    return model_step(arm_model(p), x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl,
+                      gamma, **kw)
 
 
 class OracleController:

@@ -3,8 +3,11 @@ constants, the asymmetric arm cases and non-uniform chains, and the GPU tests' h
 imports without either).
 
 The yardsticks themselves live in ``oracle/``: ``mppi_oracle.py`` (the arm, with torque limits and workspace
-obstacles) and ``chain_oracle.py`` (the chain, with torque limits), pinned to these fixtures by
-test_oracle_golden.py, test_clamp_cpu.py, test_chain_clamp_cpu.py, test_obstacle_cpu.py and test_chain_oracle.py.
+obstacles, at rest or moving; the one collision-cost loop and step of either model, ``discs_at``, ``moving_masks``)
+and ``chain_oracle.py`` (the chain, with torque limits and the same obstacles through ``chain_collides``;
+``chain_segment_test``, ``chain_touch_mask``, ``chain_moving_masks``), pinned to these fixtures by
+test_oracle_golden.py, test_clamp_cpu.py, test_chain_clamp_cpu.py, test_obstacle_cpu.py, test_chain_obstacle_cpu.py,
+test_moving_obstacle_cpu.py, test_chain_moving_obstacle_cpu.py and test_chain_oracle.py.
 """
 import glob
 import os

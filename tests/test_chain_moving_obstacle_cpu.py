@@ -1,8 +1,9 @@
 """CPU: moving obstacles for the n-link chain.
 
-  * the chain yardstick of tests/moving_obstacle_ref.py at n = 2 with ChainParams.from_arm2() against every
-    move_step_* fixture captured from the reference (S to 1e-12 relative, every flag equal) and against the arm's;
-  * zero velocities are chain_obstacle_ref.chain_obstacle_costs, bit for bit, at n = 2, 3 and 7;
+  * oracle/chain_oracle.py's moving discs (O.collision_costs on chain_model with vel=) at n = 2 with
+    ChainParams.from_arm2() against every move_step_* fixture captured from the reference (S to 1e-12 relative, every
+    flag equal) and against the arm's;
+  * zero velocities are the static definition (vel=None), bit for bit, at n = 2, 3 and 7;
   * chain_moving_masks (what the GPU tests evaluate on the device's recorded directions) agrees with the rollout's flags;
   * ChainMPPIController's validation of obstacle_velocities and its by-value comparison key;
   * the C ABI: mppi_chain_set_moving_obstacles is declared and exported, and refuses a null context.
@@ -15,8 +16,7 @@ import numpy as np
 import pytest
 
 import chain_oracle as CO
-import moving_obstacle_ref as MR
-from chain_obstacle_ref import chain_obstacle_costs
+import mppi_oracle as O
 from conftest import GOLDEN, ROOT
 from mppi_robotarm_amd.chain import ChainMPPIController, ChainParams
 
@@ -39,13 +39,13 @@ def test_chain_yardstick_at_two_links_matches_the_reference(name, paths):
     g = _load(name)
     kw = dict(lo=g.get("u_min"), hi=g.get("u_max"), discs=g["obstacles"], vel=g["obstacle_velocities"],
               obstacle_cost=float(g["obstacle_cost"]))
-    r = MR.chain_moving_step(*_args(g, paths[str(g["path"])]), CO.ChainParams.from_arm2(), **kw)
+    r = CO.step(*_args(g, paths[str(g["path"])]), CO.ChainParams.from_arm2(), **kw)
     assert np.array_equal(r["flag"], g["flag"])
     np.testing.assert_allclose(r["clear"], g["clearance"], rtol=1e-9, atol=1e-13)
     assert float(np.max(np.abs(r["S"] - g["S"]) / np.abs(g["S"]))) < 1e-12
     assert int(np.argmin(r["S"])) == int(np.argmin(g["S"]))
     np.testing.assert_allclose(r["u_seq"], g["u_seq"], rtol=1e-10, atol=1e-10)
-    arm = MR.moving_costs(*_args(g, paths[str(g["path"])]), **kw)
+    arm = O.rollout_costs(*_args(g, paths[str(g["path"])]), details=True, **kw)
     assert np.array_equal(r["flag"], arm["flag"]) and np.array_equal(r["hits"], arm["hits"])
     assert float(np.max(np.abs(r["S"] - arm["S"]) / np.abs(arm["S"]))) < 1e-12
 
@@ -65,22 +65,23 @@ def test_zero_velocity_is_the_static_chain_yardstick_bit_for_bit(n, paths):
     discs = np.array([[tip[0] + 0.02, tip[1], 0.03], [0.3, 0.3, 0.1]])
     args = (x0, u, eps, paths["xydq_circle"], 40, 0.03, 100.0, 0.98, np.eye(n) * 4.0, [0.5, 0.5, 5.0, 5.0],
             [5.0, 5.0, 50.0, 50.0], 0.0, P)
-    want = chain_obstacle_costs(*args, discs=discs, obstacle_cost=7.0)
+    want = CO.chain_rollout_costs(*args, discs=discs, obstacle_cost=7.0, details=True)
     assert want["flag"].any() and not want["flag"].all()
     for vel in (None, np.zeros((2, 2))):
-        got = MR.chain_moving_costs(*args, discs=discs, vel=vel, obstacle_cost=7.0)
+        got = CO.chain_rollout_costs(*args, discs=discs, vel=vel, obstacle_cost=7.0, details=True)
         for k in ("S", "S_track", "flag", "clear", "hits"):
             assert np.array_equal(got[k], want[k]), k
-    moved = MR.chain_moving_costs(*args, discs=discs, vel=np.array([[0.5, 0.0], [0.0, 0.0]]), obstacle_cost=7.0)
+    moved = CO.chain_rollout_costs(*args, discs=discs, vel=np.array([[0.5, 0.0], [0.0, 0.0]]), obstacle_cost=7.0,
+                                   details=True)
     assert not np.array_equal(moved["flag"], want["flag"])
     # the masks from recorded directions are the rollout's flags, and a step off they are not
     th = np.cumsum(moved["q"], -1)
     dirs = np.concatenate([np.cos(th), np.sin(th)], -1)
     vel = np.array([[0.5, 0.0], [0.0, 0.0]])
-    mask, gap = MR.chain_moving_masks(dirs, discs, vel, 0.03, P.fk)
+    mask, gap = CO.chain_moving_masks(dirs, discs, vel, 0.03, P.fk)
     assert np.array_equal(mask != 0, moved["flag"])
     np.testing.assert_allclose(gap.reshape(K, T, -1).min(-1), moved["clear"], rtol=1e-9, atol=1e-13)
-    assert not np.array_equal(MR.chain_moving_masks(dirs, discs, vel, 0.03, P.fk, shift=-1)[0], mask)
+    assert not np.array_equal(CO.chain_moving_masks(dirs, discs, vel, 0.03, P.fk, shift=-1)[0], mask)
 
 
 # ---------------------------------------------------------------- the drop-in's key logic

@@ -1,9 +1,9 @@
 """CPU: workspace obstacles for the n-link chain (a collision cost on every link).
 
-  * tests/chain_obstacle_ref.py, the fp64 yardstick of the GPU tests, reduces at n = 2 with ChainParams.from_arm2()
-    to oracle/mppi_oracle.py's arm definition (itself pinned to the reference's own obst_* fixtures by
-    test_obstacle_cpu.py): distances, flags, hit counts and S to 1e-12, test_chain_oracle.py's chain-against-arm
-    tolerance;
+  * oracle/chain_oracle.py's collision cost (chain_collides in O.collision_costs), the fp64 yardstick of the GPU tests,
+    reduces at n = 2 with ChainParams.from_arm2() to oracle/mppi_oracle.py's arm definition (itself pinned to the
+    reference's own obst_* fixtures by test_obstacle_cpu.py): distances, flags, hit counts and S to 1e-12,
+    test_chain_oracle.py's chain-against-arm tolerance;
   * its bookkeeping: hits = flag.sum(1) + flag[:, -1], S = S_track + w hits, the masks' bit layout, hand-checked
     poses of a 3-link chain;
   * the C ABI: both entry points declared in the header, bound by _native and exported by the library;
@@ -18,8 +18,7 @@ import pytest
 
 import chain_oracle as CO
 import mppi_oracle as O
-from chain_obstacle_ref import (chain_collides, chain_obstacle_costs, chain_obstacle_step, chain_segment_test,
-                                chain_touch_mask)
+from chain_oracle import chain_collides, chain_segment_test, chain_touch_mask
 from conftest import ROOT
 from helpers import OBST_STEPS, load_obst_step
 from mppi_robotarm_amd.chain import ChainMPPIController, ChainParams
@@ -30,11 +29,11 @@ TOL = 1e-12
 
 
 def _costs(g, path, P=None):
-    return chain_obstacle_costs(g["x0"], g["u_prev"], g["eps"].astype(np.float64), path, int(g["prev_idx_after"]),
-                                float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
-                                g["stage_cost_weight"], g["terminal_cost_weight"], float(g["param_exploration"]),
-                                CO.ChainParams.from_arm2() if P is None else P, lo=g.get("u_min"), hi=g.get("u_max"),
-                                discs=g["obstacles"], obstacle_cost=float(g["obstacle_cost"]))
+    return CO.chain_rollout_costs(g["x0"], g["u_prev"], g["eps"].astype(np.float64), path, int(g["prev_idx_after"]),
+                                  float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
+                                  g["stage_cost_weight"], g["terminal_cost_weight"], float(g["param_exploration"]),
+                                  CO.ChainParams.from_arm2() if P is None else P, lo=g.get("u_min"), hi=g.get("u_max"),
+                                  discs=g["obstacles"], obstacle_cost=float(g["obstacle_cost"]), details=True)
 
 
 @pytest.mark.parametrize("name", OBST_STEPS)
@@ -80,17 +79,17 @@ def test_hits_and_the_decomposition(name, paths):
     assert r["hits"].max() <= int(g["T"]) + 1
     assert float(np.max(np.abs(r["S"] - (r["S_track"] + w * r["hits"])) / np.abs(r["S"]))) < TOL
     # the step wrapper: its own hits give the reference's update; substituted hits move S by exact multiples of w
-    s = chain_obstacle_step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), paths[str(g["path"])],
-                            int(g["prev_idx_after"]), float(g["delta_t"]), float(g["param_lambda"]),
-                            float(g["param_alpha"]), g["sigma"], g["stage_cost_weight"], g["terminal_cost_weight"],
-                            float(g["param_exploration"]), CO.ChainParams.from_arm2(), discs=g["obstacles"],
-                            obstacle_cost=w)
+    s = CO.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), paths[str(g["path"])],
+                int(g["prev_idx_after"]), float(g["delta_t"]), float(g["param_lambda"]),
+                float(g["param_alpha"]), g["sigma"], g["stage_cost_weight"], g["terminal_cost_weight"],
+                float(g["param_exploration"]), CO.ChainParams.from_arm2(), discs=g["obstacles"],
+                obstacle_cost=w)
     assert float(np.max(np.abs(s["u_seq"] - g["u_seq"])) / max(1.0, float(np.max(np.abs(g["u_seq"]))))) < 1e-9
-    z = chain_obstacle_step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), paths[str(g["path"])],
-                            int(g["prev_idx_after"]), float(g["delta_t"]), float(g["param_lambda"]),
-                            float(g["param_alpha"]), g["sigma"], g["stage_cost_weight"], g["terminal_cost_weight"],
-                            float(g["param_exploration"]), CO.ChainParams.from_arm2(), discs=g["obstacles"],
-                            obstacle_cost=w, hits=np.zeros(int(g["K"])))
+    z = CO.step(g["x0"], g["u_prev"], g["eps"].astype(np.float64), paths[str(g["path"])],
+                int(g["prev_idx_after"]), float(g["delta_t"]), float(g["param_lambda"]),
+                float(g["param_alpha"]), g["sigma"], g["stage_cost_weight"], g["terminal_cost_weight"],
+                float(g["param_exploration"]), CO.ChainParams.from_arm2(), discs=g["obstacles"],
+                obstacle_cost=w, hits=np.zeros(int(g["K"])))
     assert np.array_equal(z["S"], z["S_track"])
 
 

@@ -1,7 +1,7 @@
 """GPU: moving obstacles for the n-link chain (mppi_chain_set_moving_obstacles; the MOVE instantiations of
 chain_rollout_kernel in its three forms: fp32 with one lane per sample, fp32 with a quad per sample, fp64).
 
-Yardstick: tests/moving_obstacle_ref.py (O.horizon_loop on chain_model with the discs at c + v (t + 1) dt), pinned to
+Yardstick: oracle/chain_oracle.py with vel= (O.collision_costs on chain_model, the discs at c + v (t + 1) dt), pinned to
 the arm's and to the reference's fixtures at n = 2 by test_chain_moving_obstacle_cpu.py.  Shapes, the shared problem
 of (n, K), EDGE(n) and the treatment of the flag's discontinuity are test_gpu_chain_obstacles.py's: masks against the
 fp64 predicate on the device's OWN directions, the penalty exactly through S = S_free + w hits with the device's own
@@ -19,7 +19,6 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import chain_oracle as CO  # noqa: E402
-import moving_obstacle_ref as MR  # noqa: E402
 import mppi_oracle as O  # noqa: E402
 from conftest import GOLDEN  # noqa: E402
 from helpers import _gpu, _urel, asym_chain_inputs  # noqa: E402, F401
@@ -48,8 +47,8 @@ def _mref(n, K, paths, discs, vel, w, lam=100.0, shift=0, hits=None, step=False)
     p = _problem(n, K, paths)
     args = (p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW, 0.0, _chains(n)[1])
     if step:
-        return MR.chain_moving_step(*args, discs=discs, vel=vel, obstacle_cost=w, hits=hits)
-    return MR.chain_moving_costs(*args, discs=discs, vel=vel, obstacle_cost=w, shift=shift)
+        return CO.step(*args, discs=discs, vel=vel, obstacle_cost=w, hits=hits)
+    return CO.chain_rollout_costs(*args, discs=discs, vel=vel, obstacle_cost=w, shift=shift, details=True)
 
 
 def _set_raw(eng, discs, vel, cost):
@@ -62,7 +61,7 @@ def _set_raw(eng, discs, vel, cost):
 
 def _compare_masks(mask, d, discs, vel, n, fk, E, what):
     nd = discs.shape[0]
-    want, gap = MR.chain_moving_masks(d, discs, vel, DT, fk)
+    want, gap = CO.chain_moving_masks(d, discs, vel, DT, fk)
     differ = ((mask[..., None, None] ^ want[..., None, None]) & _bits(nd, n)) != 0
     worst = float(gap[differ].max()) if differ.any() else 0.0
     print(f"{what}: {float(np.mean(mask != 0)):.1%} of the states collide, {int(differ.sum())} bits differ "
@@ -111,7 +110,7 @@ def test_masks_on_the_devices_own_directions(precision, lps, K, n, nd, paths):
     fk = _chains(n)[1].fk
     # the inputs, by the fp64 yardstick alone: >= 99.5 % of the pairs lie outside EDGE, where no bit may differ
     th = np.cumsum(p["free"]["q"], -1)
-    ref_mask, ref_gap = MR.chain_moving_masks(np.concatenate([np.cos(th), np.sin(th)], -1), discs, vel, DT, fk)
+    ref_mask, ref_gap = CO.chain_moving_masks(np.concatenate([np.cos(th), np.sin(th)], -1), discs, vel, DT, fk)
     assert float(np.mean(ref_gap > E)) >= 0.995
     r = _mref(n, K, paths, discs, vel, 0.0)
     assert np.array_equal(ref_mask != 0, r["flag"])
@@ -176,7 +175,7 @@ def test_time_index(precision, lps, K, n, paths):
     E = (6 + 2 * n) * 2.0 ** -24 * (float(np.hypot(*discs[0, :2])) + 2.0)   # edge(): this disc starts further out
     _compare_masks(mask, d, discs, vel, n, fk, E, f"{precision} lps {lps} n {n} fast")
     for shift in (-1, 1):
-        off, _ = MR.chain_moving_masks(d, discs, vel, DT, fk, shift=shift)
+        off, _ = CO.chain_moving_masks(d, discs, vel, DT, fk, shift=shift)
         assert float(np.mean((off != mask).any(1))) >= 0.10, shift
     hits = _hits_from_masks(mask)
     assert np.array_equal(S, S_free + w * hits.astype(np.float64))      # the final state counted with step T - 1's
@@ -225,7 +224,7 @@ def _asym_problem(n, K, paths):
         rng = np.random.default_rng(300 * n + K)
         eps = (rng.normal(size=(K, T, n)) @ np.linalg.cholesky(sig).T).astype(np.float32).astype(np.float64)
         args = (x0, u, eps, paths["xydq_circle"], 40, DT, 3.0e6, ALPHA, sig, W, TW, 0.0, Po)
-        free = MR.chain_moving_costs(*args)
+        free = CO.chain_rollout_costs(*args, details=True)
         discs, vel = _arrive(place_discs(free, Po))
         _asym[(n, K)] = dict(P=P, Po=Po, x0=x0, sig=sig, u=u, eps=eps, args=args, discs=discs, vel=vel)
     return _asym[(n, K)]
@@ -245,7 +244,7 @@ def test_non_uniform_chain_against_the_yardstick(precision, lps, K, n, paths):
     S, weps = _S(eng, noise), eng.weighted_noise()
     hits = _hits_from_masks(eng.obstacle_hits(noise)[0])
     eng.close()
-    r = MR.chain_moving_step(*a["args"], discs=a["discs"], vel=a["vel"], obstacle_cost=w, hits=hits)
+    r = CO.step(*a["args"], discs=a["discs"], vel=a["vel"], obstacle_cost=w, hits=hits)
     assert 0.10 <= float(np.mean(r["flag"].any(1))) <= 0.90
     assert float(np.mean(hits == r["hits"])) >= 0.99
     rel = np.abs(S - r["S"]) / np.abs(r["S"])
@@ -296,11 +295,11 @@ def test_chain_at_n2_reproduces_the_moving_reference_steps(name, precision, path
     assert rel < S_TOL
     assert c.prev_waypoints_idx == int(g["prev_idx_after"])
     w = float(g["obstacle_cost"])
-    r = MR.chain_moving_costs(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]),
-                              float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
-                              g["stage_cost_weight"], g["terminal_cost_weight"], float(g["param_exploration"]),
-                              CO.ChainParams.from_arm2(), lo=g.get("u_min"), hi=g.get("u_max"), discs=g["obstacles"],
-                              vel=g["obstacle_velocities"], obstacle_cost=w)
+    r = CO.chain_rollout_costs(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]),
+                               float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
+                               g["stage_cost_weight"], g["terminal_cost_weight"], float(g["param_exploration"]),
+                               CO.ChainParams.from_arm2(), lo=g.get("u_min"), hi=g.get("u_max"), discs=g["obstacles"],
+                               vel=g["obstacle_velocities"], obstacle_cost=w, details=True)
     hits = np.rint((S - r["S_track"]) / w)
     assert float(np.mean(hits == r["hits"])) >= 0.99
     assert float(np.mean(hits != g["hits_rest"])) >= 0.50      # not the static feature

@@ -1,7 +1,7 @@
 """GPU: workspace obstacles for the n-link chain (mppi_chain_set_obstacles; the OBST instantiations of
 chain_rollout_kernel in its three forms: fp32 with one lane per sample, fp32 with a quad per sample, fp64).
 
-Yardstick: tests/chain_obstacle_ref.py (O.horizon_loop on chain_model with the collision penalty), pinned to the arm's
+Yardstick: oracle/chain_oracle.py (O.collision_costs on chain_model with chain_collides), pinned to the arm's
 oracle and the reference's own fixtures at n = 2 by test_chain_obstacle_cpu.py.
 
 Shapes, the smallest at which each form can go wrong: n in {2, 3, 7} (even; odd, with the quad's pad link; config
@@ -34,8 +34,7 @@ pytestmark = pytest.mark.gpu
 
 import chain_oracle as CO  # noqa: E402
 import mppi_oracle as O  # noqa: E402
-from chain_obstacle_ref import (chain_collides, chain_obstacle_costs, chain_obstacle_step,  # noqa: E402
-                                chain_segment_test, chain_touch_mask)
+from chain_oracle import chain_collides, chain_segment_test, chain_touch_mask  # noqa: E402
 from helpers import OBST_STEPS, _gpu, _inside, _urel, load_obst_step  # noqa: E402, F401
 
 U_TOL = 1e-4
@@ -76,8 +75,8 @@ _prob = {}
 
 def _ref(n, K, paths, discs, w, lam=100.0, lo=None, hi=None):
     p = _prob[(n, K)]
-    return chain_obstacle_costs(p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW,
-                                0.0, _chains(n)[1], lo=lo, hi=hi, discs=discs, obstacle_cost=w)
+    return CO.chain_rollout_costs(p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW,
+                                  0.0, _chains(n)[1], lo=lo, hi=hi, discs=discs, obstacle_cost=w, details=True)
 
 
 def place_discs(free, Po):
@@ -307,8 +306,8 @@ def test_no_limits_is_wide_limits_bit_for_bit(precision, lps, K, n, paths):
 def _with_device_hits(n, K, paths, discs, w, lam, hits, lo=None, hi=None):
     """The yardstick's step with the device's hit counts in place of its own: a boundary tie cannot move a weight."""
     p = _prob[(n, K)]
-    return chain_obstacle_step(p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW,
-                               0.0, _chains(n)[1], lo=lo, hi=hi, discs=discs, obstacle_cost=w, hits=hits)
+    return CO.step(p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW,
+                   0.0, _chains(n)[1], lo=lo, hi=hi, discs=discs, obstacle_cost=w, hits=hits)
 
 
 @pytest.mark.parametrize("lam,w", [(100.0, 1.0e10), (3.0e6, 3.0e6)])
@@ -374,11 +373,11 @@ def test_chain_at_n2_reproduces_the_obstructed_reference_steps(name, paths):
         assert _urel(u_seq, g["u_seq"]) < U_TOL and _urel(u0, g["u0"]) < U_TOL
     else:
         w = float(g["obstacle_cost"])
-        r = chain_obstacle_costs(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]),
-                                 float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
-                                 g["stage_cost_weight"], g["terminal_cost_weight"], float(g["param_exploration"]),
-                                 CO.ChainParams.from_arm2(), lo=g.get("u_min"), hi=g.get("u_max"),
-                                 discs=g["obstacles"], obstacle_cost=w)
+        r = CO.chain_rollout_costs(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]),
+                                   float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
+                                   g["stage_cost_weight"], g["terminal_cost_weight"], float(g["param_exploration"]),
+                                   CO.ChainParams.from_arm2(), lo=g.get("u_min"), hi=g.get("u_max"),
+                                   discs=g["obstacles"], obstacle_cost=w, details=True)
         hits = np.rint((S - r["S_track"]) / w)
         assert float(np.mean(hits == r["hits"])) >= 0.99
         up = O.update(r["S_track"] + w * hits, g["u_prev"], eps, float(g["param_lambda"]), g["x0"],

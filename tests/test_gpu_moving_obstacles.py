@@ -1,6 +1,6 @@
 """GPU: moving obstacles (mppi_set_moving_obstacles) on the 2-link arm, through every layer.
 
-The yardstick is tests/moving_obstacle_ref.py (the fp64 oracle with the discs at c + v (t + 1) dt), pinned on the CPU
+The yardstick is oracle/mppi_oracle.py with vel= (the fp64 oracle with the discs at c + v (t + 1) dt), pinned on the CPU
 to the move_* fixtures captured from the reference (test_moving_obstacle_cpu.py).  Tolerances and the treatment of
 the collision flag's discontinuity are test_gpu_obstacles.py's: masks are compared with the fp64 predicate on the
 device's OWN recorded directions (bits may differ only within 4e-6 m of a boundary, on at most 0.5 % of the pairs),
@@ -17,7 +17,6 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-import moving_obstacle_ref as MR  # noqa: E402
 import mppi_oracle as O  # noqa: E402
 from conftest import GOLDEN  # noqa: E402
 from helpers import RUNPY, X0, _ctrl, _engine, _gpu, _urel, _window  # noqa: E402, F401
@@ -52,9 +51,9 @@ def _arrive(p, T, n=8):
 
 def _mref(K, T, paths, discs, vel, w, lam=100.0, shift=0, eps=None):
     p = _problem(K, T, paths)
-    return MR.moving_costs(X0, _u(T), p["eps"] if eps is None else eps, paths["xydq_circle"], 0, DT, lam, 0.98,
+    return O.rollout_costs(X0, _u(T), p["eps"] if eps is None else eps, paths["xydq_circle"], 0, DT, lam, 0.98,
                            RUNPY["sigma"], RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"], discs=discs,
-                           vel=vel, obstacle_cost=w, shift=shift)
+                           vel=vel, obstacle_cost=w, shift=shift, details=True)
 
 
 def _set_moving_raw(eng, discs, vel, cost):
@@ -118,7 +117,7 @@ def test_at_rest_is_the_static_feature_bit_for_bit(lps, handoff, paths, monkeypa
 
 def _compare_masks(mask, d, discs, vel, what):
     n = discs.shape[0]
-    want, gap = MR.moving_masks(d, discs, vel, DT)
+    want, gap = O.moving_masks(d, discs, vel, DT)
     bits = (np.uint32(1) << np.arange(2 * n, dtype=np.uint32)).reshape(n, 2)
     differ = ((mask[..., None, None] ^ want[..., None, None]) & bits) != 0
     assert not np.any(differ & (gap > EDGE)), f"{what}: a bit differs at clearance {float(gap[differ].max()):.2e} m"
@@ -186,8 +185,8 @@ def _fast_problem(K, T, paths):
         eng = _engine(K, T, sigma=_sigma(T))
         eps = eng.philox_noise(42, 3).cpu().numpy().transpose(1, 0, 2).astype(np.float64)
         eng.close()
-        free = MR.moving_costs(X0, _u(T), eps, paths["xydq_circle"], 0, DT, 100.0, 0.98, _sigma(T),
-                               RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"])
+        free = O.rollout_costs(X0, _u(T), eps, paths["xydq_circle"], 0, DT, 100.0, 0.98, _sigma(T),
+                               RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"], details=True)
         _fast[(K, T)] = (eps, free)
     return _fast[(K, T)]
 
@@ -204,12 +203,12 @@ def test_time_index(K, T, lps, paths):
     kw = dict(discs=discs, vel=vel, obstacle_cost=0.0)
     args = (X0, _u(T), eps, paths["xydq_circle"], 0, DT, 100.0, 0.98, _sigma(T), RUNPY["stage_cost_weight"],
             RUNPY["terminal_cost_weight"])
-    r = MR.moving_costs(*args, **kw)
+    r = O.rollout_costs(*args, details=True, **kw)
     share = float(np.mean(r["flag"].any(1)))
     assert 0.10 <= share <= 0.90
     # the CPU side: either off-by-one definition changes the masks of >= 10 % of the samples
     for shift in (-1, 1):
-        off = MR.moving_costs(*args, shift=shift, **kw)
+        off = O.rollout_costs(*args, shift=shift, details=True, **kw)
         assert float(np.mean((off["flag"] != r["flag"]).any(1))) >= 0.10, shift
     w = 7.0
     eng = _engine(K, T, lps=lps, sigma=_sigma(T))
@@ -227,7 +226,7 @@ def test_time_index(K, T, lps, paths):
     agree = float(np.mean(((mask != 0) == r["flag"]).all(1)))
     assert agree >= 0.99
     for shift in (-1, 1):
-        off, _ = MR.moving_masks(d, discs, vel, DT, shift=shift)
+        off, _ = O.moving_masks(d, discs, vel, DT, shift=shift)
         assert float(np.mean((off != mask).any(1))) >= 0.10, shift
     assert np.array_equal(mask, want) or float(np.mean(mask != want)) <= EDGE_CAP
     # the rollout counted what the debug kernel saw: every step's flag and the last one once more (T dt = step T - 1)
@@ -343,11 +342,11 @@ def test_moving_step_matches_reference(name, how, paths):
     assert c.prev_waypoints_idx == int(g["prev_idx_after"])
     # the device's own hit counts (S_dev - S_track, exact multiples of w)
     w = float(g["obstacle_cost"])
-    r = MR.moving_costs(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]),
+    r = O.rollout_costs(g["x0"], g["u_prev"], eps, paths[str(g["path"])], int(g["prev_idx_after"]),
                         float(g["delta_t"]), float(g["param_lambda"]), float(g["param_alpha"]), g["sigma"],
                         g["stage_cost_weight"], g["terminal_cost_weight"], float(g["param_exploration"]),
                         lo=g.get("u_min"), hi=g.get("u_max"), discs=g["obstacles"], vel=g["obstacle_velocities"],
-                        obstacle_cost=w)
+                        obstacle_cost=w, details=True)
     hits = np.rint((c.last_S - r["S_track"]) / w)
     assert float(np.mean(hits == r["hits"])) >= 0.99
     assert float(np.mean(hits != g["hits_rest"])) >= 0.50     # not the static feature: the same discs at rest
@@ -392,9 +391,9 @@ def test_moving_closed_loop_ticks(paths):
         window = paths["xydq_circle"][c.prev_waypoints_idx:c.prev_waypoints_idx + 30]
         c._engine.set_step_inputs(g["states"][i], window, u_prev)
         slots, _ = c._engine.nearest_slots(c._noise_dev)
-        r = MR.moving_costs(g["states"][i], u_prev, eps, paths["xydq_circle"], c.prev_waypoints_idx, DT, 100.0, 0.98,
+        r = O.rollout_costs(g["states"][i], u_prev, eps, paths["xydq_circle"], c.prev_waypoints_idx, DT, 100.0, 0.98,
                             RUNPY["sigma"], RUNPY["stage_cost_weight"], RUNPY["terminal_cost_weight"],
-                            discs=discs, vel=vel, obstacle_cost=w)
+                            discs=discs, vel=vel, obstacle_cost=w, details=True)
         delta, gap, differ = waypoint_pick_delta(r, slots, window, RUNPY["stage_cost_weight"],
                                                  RUNPY["terminal_cost_weight"])
         ref = g["S"][i] + delta
