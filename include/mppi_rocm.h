@@ -588,6 +588,41 @@ int mppi_chain_set_moving_obstacles(mppi_chain_ctx *ctx, int n, const double *di
 int mppi_chain_debug_obstacle_hits(mppi_chain_ctx *ctx, const float *noise_dev, int K,
                                    unsigned long long *mask_dev, float *dir_dev);
 
+/* Self-collision for the chain: a cost on every pair of non-adjacent links.  With the
+ * joints b_a of mppi_chain_set_obstacles, link a is the zero-thickness segment
+ * [b_{a-1}, b_a].  For every pair a < b with b >= a + 2: e(a, b) is the smallest of
+ * the four endpoint-to-segment distances (the projection clipped to the segment) and
+ * x(a, b) holds when the segments cross properly (the two ends of each strictly on
+ * opposite sides of the other's line); the pair is in self-collision when x(a, b) or
+ * e(a, b) < clearance (the links' thickness, centre line to centre line; 0 counts
+ * crossings only).  Adjacent links share a joint and are never tested.  A state
+ * self-collides when any pair does: every step of the horizon whose new state
+ * self-collides adds `cost` to its sample's S and the final state adds it once more,
+ *   S = S_track + obstacle_cost * hits_disc + cost * hits_self,
+ * each count in [0, T + 1], the two products added in that order, each one fp64
+ * multiply and add after the terminal cost.  Evaluated in the rollout's own precision
+ * on the (cos, sin) the step produced; clearance^2 is the fp64 product, rounded once to
+ * fp32 for the fp32 rollouts.  Discs, moving discs, torque limits and self-collision
+ * combine in one launch.
+ * enable = 0 restores exactly the kernels launched before (clearance and cost are
+ * still checked).  At n = 2 there is no pair: the call is accepted and changes nothing.
+ * No device call: in effect from the next launch of any kind (a by-value kernel input,
+ * so a captured graph freezes it).  MPPI_E_ARG for a NaN, negative or infinite
+ * clearance or cost ("self collision" in mppi_last_error) and when the kernel it
+ * would need does not fit a CU; the setting in effect is then kept. */
+int mppi_chain_set_self_collision(mppi_chain_ctx *ctx, int enable, double clearance, double cost);
+
+/* Tests: the self-collision test of the first K samples at every step as the
+ * context's rollout evaluates it (its precision, its lanes per sample, its step and
+ * its hit function) on the current step inputs, the clearance in effect and noise_dev.
+ * mask_dev[K][T] (uint32 device): bit i is pair i in the enumeration a ascending, then
+ * b ascending ((0,2), (0,3), ..., (1,3), ...: 15 bits at n = 7); bits of pairs that do
+ * not exist are never set (n = 2: all zero).  dir_dev[K][T][2 n] as
+ * mppi_chain_debug_obstacle_hits lays it out.  Nothing of the context's step state
+ * changes.  mppi_chain_debug_slots refuses while self-collision is enabled. */
+int mppi_chain_debug_self_hits(mppi_chain_ctx *ctx, const float *noise_dev, int K, unsigned *mask_dev,
+                               float *dir_dev);
+
 /* ------------------------------------------------------------------------
  * The reference's own noise on the device: NumPy's legacy global-RNG stream of
  * np.random.multivariate_normal(mu, Sigma, (K, T)) (control.py:154-164), the

@@ -49,6 +49,7 @@ EXPORTS = (
     "mppi_chain_noise_philox", "mppi_chain_sync", "mppi_chain_debug_set_buffer", "mppi_chain_debug_slots",
     "mppi_chain_wait_outputs", "mppi_chain_optimal_traj_host", "mppi_chain_last_eta",
     "mppi_chain_set_obstacles", "mppi_chain_set_moving_obstacles", "mppi_chain_debug_obstacle_hits",
+    "mppi_chain_set_self_collision", "mppi_chain_debug_self_hits",
     "mppi_config_init", "mppi_chain_config_init",
     "mppi_np_ctx_create", "mppi_np_ctx_destroy", "mppi_np_plan", "mppi_np_set_jumps", "mppi_np_draw",
     "mppi_np_draw_result", "mppi_readback_create", "mppi_readback_destroy", "mppi_readback_run",
@@ -203,6 +204,8 @@ def open_library(path: str):
         "mppi_chain_set_obstacles": ([vp, C.c_int, dp, C.c_double], C.c_int),
         "mppi_chain_set_moving_obstacles": ([vp, C.c_int, dp, dp, C.c_double], C.c_int),
         "mppi_chain_debug_obstacle_hits": ([vp, fp, C.c_int, vp, fp], C.c_int),
+        "mppi_chain_set_self_collision": ([vp, C.c_int, C.c_double, C.c_double], C.c_int),
+        "mppi_chain_debug_self_hits": ([vp, fp, C.c_int, vp, fp], C.c_int),
         "mppi_config_init": ([C.POINTER(ConfigC)], None),
         "mppi_np_ctx_create": ([C.c_int, vp, C.POINTER(vp)], C.c_int),
         "mppi_np_ctx_destroy": ([vp], None),

@@ -18,6 +18,7 @@ multi-GPU set-up from ``controller_base.MPPIControllerBase``.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -137,6 +138,54 @@ class ChainEngine(_Engine):
                                               C.byref(lps)), "mppi_chain_ctx_info")
         self.blocks, self.threads, self.lanes_per_sample = blocks.value, threads.value, lps.value
         self.handoff = "poll" if poll.value else "counter"
+        # what set_self_collision last gave the context: the clearance (None: disabled) and the cost
+        self.self_clearance, self.self_collision_cost = None, 0.0
+        # (resolved leniently, as set_moving_obstacles: the tools build engines on an older build of the library)
+        self._c_set_self_collision = getattr(self._lib, "mppi_chain_set_self_collision", None)
+
+    # -- self-collision (mppi_chain_set_self_collision) ------------------------
+    @staticmethod
+    def check_self_collision(clearance, cost) -> tuple[float | None, float]:
+        """(clearance as a float or None for disabled, cost as a float), or ValueError: a clearance that is NaN,
+        negative or infinite, a cost that is NaN, negative or infinite (checked with the feature disabled too)."""
+        try:
+            d = None if clearance is None else float(clearance)
+            w = float(cost)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"self collision: {e}") from None
+        if d is not None and not (d >= 0.0 and math.isfinite(d)):
+            raise ValueError("self_clearance must be finite and >= 0 (None disables the self-collision cost)")
+        if not (w >= 0.0 and math.isfinite(w)):
+            raise ValueError("self_collision_cost must be finite and >= 0")
+        return d, w
+
+    def set_self_collision(self, clearance, cost: float = 1.0e10) -> None:
+        """The cost on non-adjacent link pairs: two links b >= a + 2 collide when they cross or come within
+        `clearance` (m, centre line to centre line; 0: crossings only), and every self-colliding step of a sample
+        adds `cost` to its S (the final state once more): mppi_chain_set_self_collision.  In effect from the next
+        launch of any kind; `clearance=None` disables it (the kernels launched before).  No device call.  A
+        2-link chain has no such pair: accepted, without effect.  ValueError for a bad value."""
+        d, w = self.check_self_collision(clearance, cost)
+        if self._c_set_self_collision is None:
+            raise ValueError("mppi_chain_set_self_collision: this build of the library has no self-collision cost")
+        N.check(self._c_set_self_collision(self._ctx, 0 if d is None else 1, 0.0 if d is None else d, w),
+                "mppi_chain_set_self_collision")
+        self.self_clearance, self.self_collision_cost = d, w
+
+    def self_hits(self, noise: torch.Tensor, K: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Tests: the self-collision test of the first K samples per step as this context's rollout evaluates it
+        (mppi_chain_debug_self_hits) -> (mask (K, T) uint32: bit i is pair i of the enumeration a ascending, then
+        b ascending, over a < b, b >= a + 2; dir (K, T, 2 n) fp32 as obstacle_hits')."""
+        self._sync_stream()
+        self._check_noise(noise)
+        K = self.K_local if K is None else int(K)
+        mask = torch.zeros((K, self.T), dtype=torch.int32, device=self.device)
+        d = torch.zeros((K, self.T, 2 * self.n), dtype=torch.float32, device=self.device)
+        N.check(self._lib.mppi_chain_debug_self_hits(self._ctx, C.c_void_p(noise.data_ptr()), K,
+                                                     C.c_void_p(mask.data_ptr()), C.c_void_p(d.data_ptr())),
+                "mppi_chain_debug_self_hits")
+        self.synchronize()
+        return mask.cpu().numpy().view(np.uint32), d.cpu().numpy()
 
     def last_eta(self) -> float:
         """eta = sum_k exp(-(S_k - min S) / lambda) of the last update (wait_outputs) or weighted noise
@@ -202,7 +251,14 @@ class ChainMPPIController(MPPIControllerBase):
     ``c + v (t + 1) delta_t``, and the caller advances ``obstacles`` between calls.  Plain attributes, compared by value on every call, so they may be edited in
     place or rebound between calls; a bad value raises ValueError before anything is drawn or moved.  Every
     engine a step runs on (``precision="auto"``'s fp64 one, every rank's of a process group) gets them before its
-    launch."""
+    launch.
+
+    ``self_clearance`` / ``self_collision_cost``: the cost on non-adjacent link pairs (mppi_chain_set_self_collision):
+    links ``a`` and ``b >= a + 2`` collide when they cross or come within ``self_clearance`` metres, centre line to
+    centre line (0: crossings only; ``None``, the default: off), and every self-colliding step of a sample, and its
+    final state once more, adds ``self_collision_cost``.  Plain attributes too, compared by value on every call and
+    pushed to whichever engine runs the step; a bad value raises ValueError before anything is drawn or moved.  A
+    2-link chain has no such pair: accepted, without effect."""
 
     ETA_TOL = 1e-6   # weight outside the best sample above which precision="auto" takes the fp64 rollout
 
@@ -215,7 +271,8 @@ class ChainMPPIController(MPPIControllerBase):
                  u_init=None, device: int | None = None, verbose: bool = False, noise: str = "numpy", seed: int = 0,
                  process_group=None, exchange: str = "auto", precision: str = "auto",
                  numpy_noise_on_device: bool = True, u_min=None, u_max=None, obstacles=None,
-                 obstacle_cost: float = 1.0e10, obstacle_velocities=None) -> None:
+                 obstacle_cost: float = 1.0e10, obstacle_velocities=None, self_clearance=None,
+                 self_collision_cost: float = 1.0e10) -> None:
         self.chain = chain
         if precision not in ("auto", "f32", "f64"):
             raise ValueError("precision must be 'auto', 'f32' or 'f64'")
@@ -241,11 +298,28 @@ class ChainMPPIController(MPPIControllerBase):
         self._obst_checked = None               # the last (obstacles bytes, cost, velocities) that passed the checks
         self._okey = None                       # this call's key (_obstacle_key), for _device_step
         self._obstacle_key()
+        self.self_clearance = self_clearance            # m between the centre lines of non-adjacent links, or None: off
+        self.self_collision_cost = self_collision_cost  # added to S per self-colliding step (and once for the final state)
+        self._skey = self._self_key()                   # this call's (clearance, cost), for _device_step
         self._slots = {}               # rollout precision -> the parked state of its engine (_SLOT fields)
         self._active = None            # the precision whose engine the per-engine fields hold
         self._spread = False           # precision="auto": the last step's weights were spread (next step fp64)
         self.last_precision = None     # the rollout precision of the last step's result
         self.last_eta = None           # and the spread of its weights (eta, mppi_chain_last_eta)
+
+    def _self_key(self):
+        """self.self_clearance / self.self_collision_cost by value, checked (ValueError): what every engine of this
+        call must hold (ChainEngine.self_clearance, self_collision_cost)."""
+        return ChainEngine.check_self_collision(self.self_clearance, self.self_collision_cost)
+
+    def _push_self_collision(self, eng, key) -> None:
+        """Give the engine this call's self-collision setting unless it holds it already (no device call either
+        way): a parked engine may hold an older one."""
+        have = (eng.self_clearance, eng.self_collision_cost)
+        if key[0] is None and have[0] is None:
+            return                                          # off stays off, whatever cost came with it
+        if key != have:
+            eng.set_self_collision(*key)
 
     @property
     def host_update(self) -> bool:
@@ -318,6 +392,7 @@ class ChainMPPIController(MPPIControllerBase):
 
     def calc_control_input(self, observed_x):
         self._okey = self._obstacle_key()                  # ValueError before anything is drawn or moved
+        self._skey = self._self_key()                      # likewise
         if self._npre is not None and self.noise_source != "numpy":
             self._settle_predraw()                         # (the NumPy path settles it after its checks)
         u = self.u_prev
@@ -377,6 +452,7 @@ class ChainMPPIController(MPPIControllerBase):
             np.linalg.inv(self.Sigma)                      # LinAlgError as control.py:106 (Sigma checked when it changes)
         eng = self._get_engine(key)
         self._push_obstacles(eng, self._okey)              # this call's discs, before any launch of this engine
+        self._push_self_collision(eng, self._skey)         # ... and its self-collision setting
         if isinstance(epsilon, DeviceDrawn):               # a device draw, into one engine's buffer
             if epsilon.buf is not self._noise_dev:
                 eng._sync_stream()

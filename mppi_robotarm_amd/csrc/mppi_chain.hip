@@ -26,6 +26,10 @@
 //    test every link against up to eight discs after every step and add cost x (colliding states) to S.  The discs
 //    travel in ChainObstK, the last argument after ChainClampK; a context without discs launches the kernels it
 //    launched before.
+//  * self-collision (mppi_chain_set_self_collision): the SELF instantiations of the CLAMP + OBST rollout kernels test
+//    every pair of non-adjacent links after every step (crossing, or closer than the clearance) and add
+//    cost x (self-colliding states) to S.  The clearance and cost travel in ChainSelfK, the last argument after
+//    ChainObstK; a context with the feature off launches the kernels it launched before.
 //
 // C ABI: include/mppi_rocm.h (mppi_chain_*).
 #include <hip/hip_runtime.h>
@@ -585,6 +589,159 @@ struct ObstDbg {
     int K;
 };
 
+// ---- self-collision (mppi_chain_set_self_collision): does a state fold onto itself.  Joint j is b_{j-1} (joint 0
+// the origin, joint N the tip), link L the segment from joint L to joint L + 1 along the unit direction
+// u_L = (cos th_L, sin th_L), in the cost's kinematics as above.  Links a < b with b >= a + 2 collide when one of
+// the four endpoint-to-segment distances is below the clearance d, or when they cross properly.  Per (joint j, link L)
+// one test: r = joint j - joint L, the projection s = r . u_L and the perpendicular offset c = u_L x r (a dot and a
+// cross product), the projection clipped to [0, fk_L] and the foot point subtracted as seg_hits does it (the squared
+// length of r - clip(s) u_L: no term at the magnitude of |r|^2 is cancelled, unlike the expanded |r|^2 - 2 s sigma +
+// sigma^2, and the same form as the yardstick's, so directions a rounding off unit length move nothing).  The links
+// cross properly when the two offsets of either link's ends from the other's line have strictly opposite signs,
+// c c' < 0 for both: the offsets computed beside the distance tests, on the same r.  A joint is tested once per link
+// that one of its own links is not adjacent to (self_need): 40 tests and 15 sign pairs at n = 7.  The rollouts keep
+// min(distance^2) and min over the pairs of max(c c', c c'), the SMASK variants (mppi_chain_debug_self_hits) the same
+// values pair by pair, so both decide on the same numbers; every product-sum is an explicit fma.
+struct ChainSelfK {
+    double d2d;   // clearance^2 in fp64 (the fp64 rollout)
+    double w;     // the cost of one self-colliding state
+    float d2;     // clearance^2 rounded once from the fp64 product (the fp32 rollouts)
+    int on;       // the host's choice of the SELF kernels; the kernels do not read it
+};
+using SelfMask = unsigned;
+// bit of the pair (a, b), a ascending, then b ascending
+constexpr int self_bit(int N, int a, int b) { return a * (N - 2) - a * (a - 1) / 2 + (b - a - 2); }
+constexpr bool self_apart(int a, int b) { return a - b >= 2 || b - a >= 2; }
+// joint j belongs to links j - 1 and j: tested against link L when one of them is not adjacent to L
+constexpr bool self_need(int N, int j, int L) { return (j >= 1 && self_apart(j - 1, L)) || (j < N && self_apart(j, L)); }
+// the i-th joint tested against link L (-1 past the last)
+constexpr int self_joint(int N, int L, int i) {
+    for (int j = 0; j <= N; ++j)
+        if (self_need(N, j, L) && i-- == 0) return j;
+    return -1;
+}
+__device__ __forceinline__ float min_raw_f32(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float max_raw_f32(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// One lane per sample, fp32: two joints per packed instruction against one link.  Returns the pair mask (SMASK) or
+// whether any pair collides.
+template <int N, bool SMASK, class KC>
+__device__ __forceinline__ SelfMask chain_self_hits(const ChainState<N>& x, const KC& k, float dd) {
+    if constexpr (N < 3) return 0;
+    float jx[N + 1], jy[N + 1];
+    jx[0] = jy[0] = 0.f;
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        const float L = k.p[kOffFk + a];
+        jx[a + 1] = fmaf(L, get(x.c, a), jx[a]);
+        jy[a + 1] = fmaf(L, get(x.s, a), jy[a]);
+    }
+    float d2[N][N + 1], cr[N][N + 1];   // [link][joint], the tested entries only
+    unroll_seq([&](auto L_c) {
+        constexpr int L = decltype(L_c)::value;
+        const f32x2 ux = splat(get(x.c, L)), uy = splat(get(x.s, L));
+        const float len = k.p[kOffFk + L];
+        unroll_seq([&](auto i_c) {
+            constexpr int i = 2 * decltype(i_c)::value;
+            constexpr int ja = self_joint(N, L, i), jn = self_joint(N, L, i + 1);
+            if constexpr (ja >= 0) {
+                constexpr int jb = jn < 0 ? ja : jn;   // an odd count: the last joint twice
+                const f32x2 rx = f32x2{jx[ja], jx[jb]} - splat(jx[L]), ry = f32x2{jy[ja], jy[jb]} - splat(jy[L]);
+                const f32x2 s = pfma(ry, uy, rx * ux);
+                const f32x2 c = pfma(rx, -uy, ry * ux);
+                const f32x2 t = {__builtin_amdgcn_fmed3f(s.x, 0.f, len), __builtin_amdgcn_fmed3f(s.y, 0.f, len)};
+                const f32x2 ox = pfma(-t, ux, rx), oy = pfma(-t, uy, ry);
+                const f32x2 d = pfma(oy, oy, ox * ox);
+                d2[L][ja] = d.x;
+                cr[L][ja] = c.x;
+                d2[L][jb] = d.y;
+                cr[L][jb] = c.y;
+            }
+        }, std::make_integer_sequence<int, (N + 2) / 2>{});
+    }, std::make_integer_sequence<int, N>{});
+    SelfMask m = 0;
+    float dmin = 0.f, xmin = 0.f;
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+#pragma unroll
+        for (int b = a + 2; b < N; ++b) {
+            const float near = min_raw_f32(min_raw_f32(d2[a][b], d2[a][b + 1]), min_raw_f32(d2[b][a], d2[b][a + 1]));
+            const float cross = max_raw_f32(cr[a][b] * cr[a][b + 1], cr[b][a] * cr[b][a + 1]);
+            if constexpr (SMASK) {
+                m |= (SelfMask)(near < dd || cross < 0.f) << self_bit(N, a, b);
+            } else {
+                const bool first = a == 0 && b == 2;
+                dmin = first ? near : min_raw_f32(dmin, near);
+                xmin = first ? cross : min_raw_f32(xmin, cross);
+            }
+        }
+    }
+    return SMASK ? m : (SelfMask)(dmin < dd || xmin < 0.f);
+}
+
+// The fp64 rollout: the same operations in doubles, joint by joint.
+template <int N, bool SMASK>
+__device__ __forceinline__ SelfMask chain_self_hits_f64(const ChainStateD<N>& x, cdouble* k, double dd) {
+    if constexpr (N < 3) return 0;
+    double jx[N + 1], jy[N + 1];
+    jx[0] = jy[0] = 0.0;
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        jx[a + 1] = fma(k[kOffFk + a], x.c[a], jx[a]);
+        jy[a + 1] = fma(k[kOffFk + a], x.s[a], jy[a]);
+    }
+    double d2[N][N + 1], cr[N][N + 1];
+#pragma unroll
+    for (int L = 0; L < N; ++L) {
+        const double len = k[kOffFk + L];
+#pragma unroll
+        for (int j = 0; j <= N; ++j) {
+            if (!self_need(N, j, L)) continue;
+            const double rx = jx[j] - jx[L], ry = jy[j] - jy[L];
+            const double s = fma(ry, x.s[L], rx * x.c[L]);
+            const double c = fma(rx, -x.s[L], ry * x.c[L]);
+            const double t = s < 0.0 ? 0.0 : (s > len ? len : s);
+            const double ox = fma(-t, x.c[L], rx), oy = fma(-t, x.s[L], ry);
+            d2[L][j] = fma(oy, oy, ox * ox);
+            cr[L][j] = c;
+        }
+    }
+    SelfMask m = 0;
+    double dmin = 0.0, xmin = 0.0;
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+#pragma unroll
+        for (int b = a + 2; b < N; ++b) {
+            const double near = min_raw_f64(min_raw_f64(d2[a][b], d2[a][b + 1]), min_raw_f64(d2[b][a], d2[b][a + 1]));
+            const double cross = max_raw_f64(cr[a][b] * cr[a][b + 1], cr[b][a] * cr[b][a + 1]);
+            if constexpr (SMASK) {
+                m |= (SelfMask)(near < dd || cross < 0.0) << self_bit(N, a, b);
+            } else {
+                const bool first = a == 0 && b == 2;
+                dmin = first ? near : min_raw_f64(dmin, near);
+                xmin = first ? cross : min_raw_f64(xmin, cross);
+            }
+        }
+    }
+    return SMASK ? m : (SelfMask)(dmin < dd || xmin < 0.0);
+}
+
+// What a self-collision debug instance of the rollout kernel records for the first K samples
+// (mppi_chain_debug_self_hits): mask[k][t] and dir[k][t][2 N] as ObstDbg's.
+struct SelfDbg {
+    SelfMask* mask;
+    float* dir;
+    int K;
+};
+
 // The fused update's median filter runs over windows of kMedRun consecutive steps per thread: thread
 // (q, d) = (tid / N, tid % N) takes the windows of t = kMedRun q .. kMedRun q + 3 of column d.
 constexpr int kMedRun = 4;
@@ -697,11 +854,14 @@ struct alignas(16) WinRowD {
 // OBST: every step's new state is tested against the discs (obd: chain_hits_f64's records, nd of them); *hits
 // receives the count of colliding states, the final one counted once more.  ODBG: the masks and directions go to od.
 // MOVE: obd holds one row of records per step (the discs at c + v (t + 1) dt), and step t reads row t.
-template <int N, bool CLAMP, bool OBST = false, bool ODBG = false, bool MOVE = false>
+// SELF: every step's new state is tested against itself (chain_self_hits_f64, clearance^2 sdd); *shits receives the
+// count of self-colliding states, the final one counted once more.  SDBG: the pair masks and directions go to sd.
+template <int N, bool CLAMP, bool OBST = false, bool ODBG = false, bool MOVE = false, bool SELF = false, bool SDBG = false>
 __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const ChainStep* st, cdouble* kd,
                                                     const float* noise, int k, float exf, WinRowD* s_wind,
                                                     int* slots, const ChainClampK& cl, const double* obd = nullptr,
-                                                    int nd = 0, int* hits = nullptr, const ObstDbg& od = ObstDbg{}) {
+                                                    int nd = 0, int* hits = nullptr, const ObstDbg& od = ObstDbg{},
+                                                    double sdd = 0.0, int* shits = nullptr, const SelfDbg& sd = SelfDbg{}) {
     const int tid = threadIdx.x, K = c.K_local, T = c.T;
     if (tid < kSlots) {
         const double* r = st->wind[tid];
@@ -716,6 +876,8 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
     double S = 0.0, ex = 0.0, ey = 0.0, e1 = 0.0, e2 = 0.0;
     int nhit = 0;            // colliding states so far (OBST)
     bool hit_last = false;   // the last step's flag: the final state counts once more
+    int nself = 0;           // self-colliding states so far (SELF)
+    bool self_last = false;
     float nx[N];
 #pragma unroll
     for (int d = 0; d < N; ++d) nx[d] = noise[(size_t)k * N + d];
@@ -741,9 +903,22 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
                     od.dir[((size_t)k * T + t) * 2 * N + N + a] = (float)x.s[a];
                 }
             }
-        } else if constexpr (OBST) {
+        } else if constexpr (OBST && !SDBG) {
             hit_last = chain_hits_f64<N, false>(obt, nd, x, kd) != 0;
             nhit += hit_last ? 1 : 0;
+        }
+        if constexpr (SDBG) {
+            if (k < sd.K) {
+                sd.mask[(size_t)k * T + t] = chain_self_hits_f64<N, true>(x, kd, sdd);
+#pragma unroll
+                for (int a = 0; a < N; ++a) {
+                    sd.dir[((size_t)k * T + t) * 2 * N + a] = (float)x.c[a];
+                    sd.dir[((size_t)k * T + t) * 2 * N + N + a] = (float)x.s[a];
+                }
+            }
+        } else if constexpr (SELF) {
+            self_last = chain_self_hits_f64<N, false>(x, kd, sdd) != 0;
+            nself += self_last ? 1 : 0;
         }
         double px, py;
         x.effector(kd, &px, &py);
@@ -767,6 +942,7 @@ __device__ __forceinline__ double chain_horizon_f64(const ChainConst& c, const C
         S += fma(kd[kOffSw], ex * ex, fma(kd[kOffSw + 1], ey * ey, fma(kd[kOffSw + 2], e1 * e1, kd[kOffSw + 3] * (e2 * e2)))) + g;
     }
     if constexpr (OBST) *hits = nhit + (hit_last ? 1 : 0);
+    if constexpr (SELF) *shits = nself + (self_last ? 1 : 0);
     // terminal cost, control.py:109
     return S + fma(kd[kOffTw], ex * ex, fma(kd[kOffTw + 1], ey * ey, fma(kd[kOffTw + 2], e1 * e1, kd[kOffTw + 3] * (e2 * e2))));
 }
@@ -847,12 +1023,19 @@ __device__ __forceinline__ float elem(f32x2 v) {
 // The pad link of an odd chain (and the links of lanes past the chain) has length 0 and sits at the end effector:
 // its comparisons are masked off, it never hits.  ODBG: the masks and directions go to od.
 // MOVE: ob.rec holds one row of records per step (stage_obst_row), and step t reads row t.
-template <int N, bool CLAMP, bool OBST = false, bool ODBG = false, bool MOVE = false>
+// SELF: lane p tests its own two links, packed as the pair it holds, against every joint of the chain; the joints are
+// the pair's base (the same prefix scan) and its middle, traded inside the quad by DPP broadcasts.  Each lane gathers
+// the "near" bits of its rows (link, joint) and the "ends on opposite sides" bits (link, other link) into one 16-bit
+// word, the quad trades the four words, and every lane holds the 8 x 8 bit matrix M[L][m]: links a, a + k cross when
+// M[a][a + k] and M[a + k][a] are both set, which for all a at once is (M >> k) & (M >> 8 k) on the diagonal bits.
+// Rows of the pad link and of lanes past the chain are masked off.  *shits, SDBG and sd as in chain_horizon_f64.
+template <int N, bool CLAMP, bool OBST = false, bool ODBG = false, bool MOVE = false, bool SELF = false, bool SDBG = false>
 __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const ChainStep* st, const float* dyn,
                                                    const float* noise, int k, float exf, float4* s_ua4,
                                                    float4* s_win, int* slots, unsigned long long* dbg,
                                                    const ChainClampK& cl, const ObstR& ob = ObstR{}, int* hits = nullptr,
-                                                   const ObstDbg& od = ObstDbg{}) {
+                                                   const ObstDbg& od = ObstDbg{}, float sdd = 0.f, int* shits = nullptr,
+                                                   const SelfDbg& sd = SelfDbg{}) {
     static_assert(N <= 8, "four link pairs");
     // the column after which the search is placed: after 2 / 3 / 4 / 5 / 6 measured 77.0 / 76.6 / 77.6 / 75.3 /
     // 77.3 us at K = 16384 (one process, profiles/r13/chain_quad_search_at_ab.txt)
@@ -981,6 +1164,88 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
             nhit += hit_last ? 1 : 0;
         }
     };
+    static_assert(!SELF || (N >= 3 && N <= 7), "the 8 x 8 bit matrix: links 0 .. 6, joints 0 .. 7");
+    int nself = 0;            // self-colliding states so far (SELF)
+    bool self_last = false;
+    // which of this lane's tests count: bit j (link a0) / 8 + j (link a1): joint j is tested against the link
+    // (self_need); bit m / 8 + m of rows: link m is a partner of the link (exists and is not adjacent)
+    unsigned needj = 0, rows = 0;
+    if constexpr (SELF) {
+#pragma unroll
+        for (int l = 0; l < 2; ++l) {
+            const int L = a0 + l;
+#pragma unroll
+            for (int j = 0; j <= N; ++j) needj |= (unsigned)(L < N && self_need(N, j, L)) << (8 * l + j);
+#pragma unroll
+            for (int m = 0; m < N; ++m) rows |= (unsigned)(L < N && self_apart(m, L)) << (8 * l + m);
+        }
+    }
+    auto quad_self = [&](int t) {
+        const float ex = fmaf(fk2.y, C.y, fk2.x * C.x), ey = fmaf(fk2.y, Sn.y, fk2.x * Sn.x);   // the pair's extent
+        const float bx = q_excl_prefix(ex, m1), by = q_excl_prefix(ey, m1);                     // joint a0
+        const float mx = fmaf(fk2.x, C.x, bx), my = fmaf(fk2.x, Sn.x, by);                      // joint a1
+        const f32x2 BX = {bx, mx}, BY = {by, my};
+        unsigned nb = 0, sb = 0;
+        f32x2 cprev = {0.f, 0.f};
+        unroll_seq([&](auto j_c) {
+            constexpr int j = decltype(j_c)::value;
+            const float Jx = (j & 1) ? qbc<j / 2>(mx) : qbc<j / 2>(bx);
+            const float Jy = (j & 1) ? qbc<j / 2>(my) : qbc<j / 2>(by);
+            const f32x2 rx = splat(Jx) - BX, ry = splat(Jy) - BY;
+            const f32x2 s = pfma(ry, Sn, rx * C);
+            const f32x2 cc = pfma(rx, -Sn, ry * C);
+            const f32x2 tc = {__builtin_amdgcn_fmed3f(s.x, 0.f, fk2.x), __builtin_amdgcn_fmed3f(s.y, 0.f, fk2.y)};
+            const f32x2 ox = pfma(-tc, C, rx), oy = pfma(-tc, Sn, ry);
+            const f32x2 d = pfma(oy, oy, ox * ox);
+            nb |= (d.x < sdd ? 1u << j : 0u) | (d.y < sdd ? 1u << (8 + j) : 0u);
+            if constexpr (j > 0) {   // the ends of link j - 1
+                const f32x2 p = cprev * cc;
+                sb |= (p.x < 0.f ? 1u << (j - 1) : 0u) | (p.y < 0.f ? 1u << (8 + j - 1) : 0u);
+            }
+            cprev = cc;
+        }, std::make_integer_sequence<int, N + 1>{});
+        nb &= needj;
+        sb &= rows;
+        auto trade = [&](unsigned w) {   // the four lanes' words: row L at bits 8 L .. 8 L + 7
+            const unsigned w0 = (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x00, 0xF, 0xF, kDppBC);
+            const unsigned w1 = (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x55, 0xF, 0xF, kDppBC);
+            const unsigned w2 = (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xAA, 0xF, 0xF, kDppBC);
+            const unsigned w3 = (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xFF, 0xF, 0xF, kDppBC);
+            return ((unsigned long long)(w2 | (w3 << 16)) << 32) | (w0 | (w1 << 16));
+        };
+        // bit 7 of a lane's first row (no link 7): one of its near bits is set
+        const unsigned long long Mn = trade(sb | (nb ? 0x80u : 0u));
+        const unsigned long long M = Mn & 0x7F7F7F7F7F7F7F7Full;
+        if constexpr (SDBG) {
+            const unsigned long long NB = trade(nb), Q = NB | (NB >> 1);   // Q[L][m]: joint m or m + 1 is near link L
+            SelfMask mk = 0;
+#pragma unroll
+            for (int a = 0; a < N; ++a)
+#pragma unroll
+                for (int b = a + 2; b < N; ++b) {
+                    const unsigned long long h = (Q >> (8 * a + b)) | (Q >> (8 * b + a)) | ((M >> (8 * a + b)) & (M >> (8 * b + a)));
+                    mk |= (SelfMask)(h & 1ull) << self_bit(N, a, b);
+                }
+            if (k < sd.K) {
+                if (sub == 0) sd.mask[(size_t)k * T + t] = mk;
+                float* dr = sd.dir + ((size_t)k * T + t) * 2 * N;
+                if (a0 < N) {
+                    dr[a0] = C.x;
+                    dr[N + a0] = Sn.x;
+                }
+                if (a1 < N) {
+                    dr[a1] = C.y;
+                    dr[N + a1] = Sn.y;
+                }
+            }
+        } else {
+            unsigned long long X = 0;
+#pragma unroll
+            for (int kk = 2; kk < N; ++kk) X |= (M >> kk) & (M >> (8 * kk));
+            self_last = ((X & 0x8040201008040201ull) | (Mn & 0x8080808080808080ull)) != 0ull;
+            nself += self_last ? 1 : 0;
+        }
+    };
     double S = 0.0;
     f32x2 S2 = {0.f, 0.f};   // this lane's two stage-cost terms
     f32x2 G2 = {0.f, 0.f};   // this lane's (gamma u^T Sigma^-1) v terms
@@ -1075,7 +1340,8 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
         THD = __builtin_elementwise_fma(f32x2{xa, xb}, splat(dt), THD);  // semi-implicit Euler (chain_oracle.py)
         TH = __builtin_elementwise_fma(THD, splat(dtr), TH);
         angles();
-        if constexpr (OBST) quad_hits(t);
+        if constexpr (OBST && !SDBG) quad_hits(t);
+        if constexpr (SELF) quad_self(t);
         {   // the pending (previous state's) stage cost, control.py:174-185; the row is taken only now (the
             // asm needs TH, this step's last dynamics result)
             f32x2 rw = prw;
@@ -1135,6 +1401,7 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
     const f32x2 te = tw2 * ee;
     S += (double)(te.x + te.y);
     if constexpr (OBST) *hits = nhit + (hit_last ? 1 : 0);
+    if constexpr (SELF) *shits = nself + (self_last ? 1 : 0);
     return q_sum_f64(S);
 }
 
@@ -1150,20 +1417,29 @@ __device__ __forceinline__ double chain_horizon_q4(const ChainConst& c, const Ch
 // ODBG (mppi_chain_debug_obstacle_hits; CLAMP and OBST): the same prologue and horizon, which record the masks and
 // directions of the first `flags` samples instead of counting (gslab: the masks, slab: the directions), and
 // nothing after the horizon.
+// SELF (mppi_chain_set_self_collision; built on the CLAMP + OBST kernels only, for N >= 3): every step's new state,
+// and the final state once more, is tested against itself; the count of self-colliding states times sk.w is added to
+// S after the discs' product, as one fp64 multiply and add.  Without discs ob.n = 0 and the scalar branch per disc
+// pair skips the disc test.  sk is the last argument, behind ob; the SELF = false instantiations never read it.
+// SDBG (mppi_chain_debug_self_hits): the same prologue and horizon, which record the pair masks and directions of
+// the first `flags` samples (gslab: the masks, slab: the directions) and nothing after the horizon.
 template <int N, bool POLL, bool F64, int LPS, bool SLOTS = false, bool CLAMP = false, bool OBST = false,
-          bool ODBG = false, bool MOVE = false>
+          bool ODBG = false, bool MOVE = false, bool SELF = false, bool SDBG = false>
 __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) void chain_rollout_kernel(
     const ChainConst c, const ChainStep* __restrict__ st, const float* __restrict__ dyn,
     const float* __restrict__ noise, double* __restrict__ S_out, double* __restrict__ slab, double* __restrict__ gslab,
     unsigned* __restrict__ counters, double* __restrict__ partial_out, double* __restrict__ w_eps_out,
     ChainStep* __restrict__ nxt, unsigned flags, const XDesc xd, unsigned* __restrict__ epoch, unsigned* __restrict__ tmo,
     unsigned long long* __restrict__ runmin, unsigned long long* __restrict__ dbg, const ChainClampK cl,
-    const ChainObstK ob) {
+    const ChainObstK ob, const ChainSelfK sk) {
     static_assert(N <= kCMax && N >= 2, "links");
     static_assert(!(SLOTS && CLAMP), "the slot-recording instances are unclamped");
     static_assert(CLAMP || !OBST, "the OBST kernels are built with CLAMP only");
     static_assert(OBST || !ODBG, "the obstacle-debug instances are OBST kernels");
     static_assert(OBST || !MOVE, "moving discs are discs");
+    static_assert(!SELF || (OBST && N >= 3), "the SELF kernels are CLAMP + OBST kernels of chains with a non-adjacent pair");
+    static_assert(SELF || !SDBG, "the self-collision debug instances are SELF kernels");
+    static_assert(!(ODBG && SDBG), "one recording at a time");
     static_assert(kMaxT <= kCT, "thread t stages step t's disc records");
     __shared__ float4 s_win[kSlots];
     __shared__ KeyPair s_keys[kKeyPairs];
@@ -1252,13 +1528,18 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     ObstDbg odbg{};
     if constexpr (ODBG) odbg = ObstDbg{reinterpret_cast<ObstMask*>(gslab), reinterpret_cast<float*>(slab), valid ? (int)flags : 0};
     int hits = 0;   // colliding states of this sample, the final one counted twice (OBST)
+    SelfDbg sdbg{};
+    if constexpr (SDBG) sdbg = SelfDbg{reinterpret_cast<SelfMask*>(gslab), reinterpret_cast<float*>(slab), valid ? (int)flags : 0};
+    int shits = 0;   // self-colliding states of this sample, the final one counted twice (SELF)
     if constexpr (F64) {
-        S = chain_horizon_f64<N, CLAMP, OBST, ODBG, MOVE>(c, st, (cdouble*)(dyn + kDynF64Off), noise, k, exf, s_wind, slots, cl,
-                                                    obd, nd, &hits, odbg);
+        S = chain_horizon_f64<N, CLAMP, OBST, ODBG, MOVE, SELF, SDBG>(c, st, (cdouble*)(dyn + kDynF64Off), noise, k, exf, s_wind,
+                                                                      slots, cl, obd, nd, &hits, odbg, sk.d2d, &shits, sdbg);
     } else if constexpr (LPS == 4) {
-        S = chain_horizon_q4<N, CLAMP, OBST, ODBG, MOVE>(c, st, dyn, noise, k, exf, s_ua4, s_win, slots, dbg, cl, od, &hits, odbg);
+        S = chain_horizon_q4<N, CLAMP, OBST, ODBG, MOVE, SELF, SDBG>(c, st, dyn, noise, k, exf, s_ua4, s_win, slots, dbg, cl, od,
+                                                                     &hits, odbg, sk.d2, &shits, sdbg);
     } else {
     bool hit_last = false;
+    bool self_last = false;
     if (tid < kSlots) s_win[tid] = st->win[tid];
     if constexpr (CLAMP) {
         if (tid < kCMax) s_vhi[tid] = dyn[kDynLimOff + kCMax + tid];
@@ -1326,10 +1607,23 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     odbg.dir[((size_t)k * T + t) * 2 * N + N + a] = get(x.s, a);
                 }
             }
-        } else if constexpr (OBST) {
+        } else if constexpr (OBST && !SDBG) {
             // on the (cos, sin) row pairs the step just produced, the ones effector() reads below
             hit_last = chain_hits<N, kObstNP1, false>(odt, x, kd) != 0;
             hits += hit_last ? 1 : 0;
+        }
+        if constexpr (SDBG) {
+            if (k < sdbg.K) {
+                sdbg.mask[(size_t)k * T + t] = chain_self_hits<N, true>(x, kd, sk.d2);
+#pragma unroll
+                for (int a = 0; a < N; ++a) {
+                    sdbg.dir[((size_t)k * T + t) * 2 * N + a] = get(x.c, a);
+                    sdbg.dir[((size_t)k * T + t) * 2 * N + N + a] = get(x.s, a);
+                }
+            }
+        } else if constexpr (SELF) {
+            self_last = chain_self_hits<N, false>(x, kd, sk.d2) != 0;
+            shits += self_last ? 1 : 0;
         }
         float px, py;
         x.effector(kd, &px, &py);
@@ -1359,10 +1653,12 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     S += (double)S4;
     S += (double)weighted_sq(ex, ey, e1, e2, c.dyn + kOffTw);  // terminal cost, control.py:109
     if constexpr (OBST) hits += hit_last ? 1 : 0;              // the final state once more
+    if constexpr (SELF) shits += self_last ? 1 : 0;
     }
-    if constexpr (ODBG) return;
+    if constexpr (ODBG || SDBG) return;
     // the penalty in one fp64 multiply and add: the count is exact, so no order of summation can change it
     if constexpr (OBST) S += ob.w * (double)hits;
+    if constexpr (SELF) S += sk.w * (double)shits;             // ... the discs' product first, then this one
 
     STAMP(1, NOW());
     if (S_out && owner) S_out[k] = S;
@@ -1623,6 +1919,9 @@ struct mppi_chain_ctx {
     ChainObstK ok{};               // workspace obstacles of the next launch (n = 0: none), mppi_chain_set_obstacles
     int obst_per_cu = 0;           // occupancy of the context's OBST rollout kernel (workgroups per CU)
     int move_per_cu = 0;           // ... and of its MOVE form
+    ChainSelfK sk{};               // self-collision of the next launch (on = 0: none), mppi_chain_set_self_collision
+    int self_per_cu = 0;           // occupancy of the context's SELF rollout kernel (n >= 3)
+    int self_move_per_cu = 0;      // ... and of its MOVE form
     mppi_host::DevBuf<ChainStep> d_step;      // [2] ping-pong
     int cur = 0;
     mppi_host::PinnedBuf<ChainStep> h_step;   // pinned staging
@@ -1655,7 +1954,10 @@ namespace {
 using mppi_host::fail;
 using mppi_host::launch_check;
 
-template <int N, bool P, bool F64, int LPS, bool CL, bool OB>
+// a chain has a pair of non-adjacent links, and with it SELF kernels, from three links on
+constexpr int kSelfMinN = 3;
+
+template <int N, bool P, bool F64, int LPS, bool CL, bool OB, bool SF = false>
 void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise, double* S, double* part, ChainStep* nxt,
                     unsigned flags, int* slots = nullptr) {
     const mppi_host::Handoff& h = c->hand;
@@ -1664,21 +1966,28 @@ void launch_rollout(mppi_chain_ctx* c, const ChainStep* cur, const float* noise,
             hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, true>), dim3(c->nblocks), dim3(kCT), 0, c->stream, c->kc,
                                cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags,
                                c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin,
-                               reinterpret_cast<unsigned long long*>(slots), c->ck, c->ok);
+                               reinterpret_cast<unsigned long long*>(slots), c->ck, c->ok, c->sk);
         return;
     }
+    auto go = [&](auto move, auto self) {
+        hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, false, CL, OB, false, move, self>), dim3(c->nblocks),
+                           dim3(kCT), 0, c->stream, c->kc, cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter,
+                           part, c->d_weps, nxt, flags, c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin, c->d_dbg, c->ck,
+                           c->ok, c->sk);
+    };
     if constexpr (OB) {
-        if (c->ok.moving) {   // a disc has a velocity: the MOVE form, which reads a row of disc records per step
-            hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, false, CL, OB, false, true>), dim3(c->nblocks),
-                               dim3(kCT), 0, c->stream, c->kc, cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter,
-                               part, c->d_weps, nxt, flags, c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin, c->d_dbg, c->ck,
-                               c->ok);
+        // a disc has a velocity: the MOVE form, which reads a row of disc records per step
+        if constexpr (SF && N >= kSelfMinN) {
+            if (c->ok.moving) go(std::true_type{}, std::true_type{});
+            else go(std::false_type{}, std::true_type{});
+            return;
+        }
+        if (c->ok.moving) {
+            go(std::true_type{}, std::false_type{});
             return;
         }
     }
-    hipLaunchKernelGGL((chain_rollout_kernel<N, P, F64, LPS, false, CL, OB>), dim3(c->nblocks), dim3(kCT), 0, c->stream,
-                       c->kc, cur, c->d_dyn, noise, S, h.d_slab, h.d_gslab, h.d_counter, part, c->d_weps, nxt, flags,
-                       c->ex.xd, h.d_epoch, h.h_tmo.dev, c->d_runmin, c->d_dbg, c->ck, c->ok);
+    go(std::false_type{}, std::false_type{});
 }
 
 // the link counts with an instantiated kernel: f(N) for N = n as an integral constant
@@ -1691,19 +2000,27 @@ void with_links(int n, F&& f) {
 // CLAMP, CLAMP + OBST).  Calls f(n, poll, f64, lps, clamp, obst), the context's instance as integral constants, in
 // the hand-off form `poll`.  With `obst` the CLAMP + OBST kernel, whether or not there are torque limits (without
 // them ChainClampK and the device copy of its fp32 limits hold -+inf, and clamp_mode 0 clips no nominal).
+// `self`: the SELF form of the CLAMP + OBST kernel (self-collision, with or without discs); f's last argument.  A
+// 2-link chain has no such kernel: its f is called with self = false.
 template <class F>
-void with_rollout(const mppi_chain_ctx* c, bool poll, bool obst, F&& f) {
+void with_rollout(const mppi_chain_ctx* c, bool poll, bool obst, bool self, F&& f) {
     using L1 = std::integral_constant<int, 1>;
     using L4 = std::integral_constant<int, 4>;
     with_links(c->n, [&](auto n) {
         mppi_host::with_bool(poll, [&](auto p) {
-            auto form = [&](auto cl, auto ob) {
-                if (c->f64) f(n, p, std::true_type{}, L1{}, cl, ob);
-                else if (c->lps == 4) f(n, p, std::false_type{}, L4{}, cl, ob);
-                else f(n, p, std::false_type{}, L1{}, cl, ob);
+            auto form = [&](auto cl, auto ob, auto sf) {
+                if (c->f64) f(n, p, std::true_type{}, L1{}, cl, ob, sf);
+                else if (c->lps == 4) f(n, p, std::false_type{}, L4{}, cl, ob, sf);
+                else f(n, p, std::false_type{}, L1{}, cl, ob, sf);
             };
-            if (obst) form(std::true_type{}, std::true_type{});
-            else mppi_host::with_bool(c->ck.mode != 0, [&](auto cl) { form(cl, std::false_type{}); });
+            if constexpr (decltype(n)::value >= kSelfMinN) {
+                if (self) {
+                    form(std::true_type{}, std::true_type{}, std::true_type{});
+                    return;
+                }
+            }
+            if (obst) form(std::true_type{}, std::true_type{}, std::false_type{});
+            else mppi_host::with_bool(c->ck.mode != 0, [&](auto cl) { form(cl, std::false_type{}, std::false_type{}); });
         });
     });
 }
@@ -1758,12 +2075,12 @@ int alloc(mppi_chain_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     int ncu = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-    with_rollout(c, true, false, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {   // always of the POLL form
+    with_rollout(c, true, false, false, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob, auto) {   // always of the POLL form
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
             &per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob>, kCT, 0);
     });
     // the kernel a launch with discs goes through: mppi_chain_set_obstacles refuses discs if it does not fit a CU
-    with_rollout(c, true, true, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {
+    with_rollout(c, true, true, false, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob, auto) {
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
             &c->obst_per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob>, kCT, 0);
         // ... and with moving discs (the per-step records: 16 KB of LDS more, 24 KB in fp64)
@@ -1771,6 +2088,19 @@ int alloc(mppi_chain_ctx* c) {
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
                 &c->move_per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob, false, true>, kCT, 0);
     });
+    // ... and the ones a launch with self-collision goes through (mppi_chain_set_self_collision refuses likewise).  The
+    // hand-off form below is fixed for the context's life, so it takes the smallest occupancy among the instances
+    // the context may come to launch: one that does not fit is refused by its setter and never launched.
+    with_rollout(c, true, true, true, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob, auto sf) {
+        if constexpr (sf) {
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                &c->self_per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob, false, false, true>, kCT, 0);
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                &c->self_move_per_cu, (const void*)chain_rollout_kernel<n, p, f64, lps, false, cl, ob, false, true, true>, kCT, 0);
+        }
+    });
+    for (int o : {c->obst_per_cu, c->move_per_cu, c->self_per_cu, c->self_move_per_cu})
+        if (o >= 1 && o < per_cu) per_cu = o;
     // behind the counters: the per-CU ticket words of the issue fairness (mppi_device.h)
     if (int rc = c->hand.setup(c->nblocks, ncu, per_cu, 2 + c->cfg.T * c->n, kCuSlots)) return rc;
     c->kc.acquire = c->hand.acquire;
@@ -2001,8 +2331,8 @@ int chain_rollout(mppi_chain_ctx* c, const float* noise_dev, double* S_dev, doub
     }
     const ChainStep* cur = c->d_step + c->cur;
     ChainStep* nxt = c->d_step + (c->cur ^ 1);
-    with_rollout(c, c->hand.poll, c->ok.n > 0, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {
-        launch_rollout<n, p, f64, lps, cl, ob>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots);
+    with_rollout(c, c->hand.poll, c->ok.n > 0, c->sk.on != 0, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob, auto sf) {
+        launch_rollout<n, p, f64, lps, cl, ob, sf>(c, cur, noise_dev, S_dev, partial_dev, nxt, flags, slots);
     });
     if (int rc = launch_check("chain_rollout_kernel")) return rc;
     note_update(c, flags);
@@ -2029,6 +2359,7 @@ int mppi_chain_debug_slots(mppi_chain_ctx* c, const float* noise_dev, double* S_
     if (c->n != kCDebugN) return fail(MPPI_E_ARG, "slot recording is built for the 7-link chain only");
     if (c->ck.mode != 0) return fail(MPPI_E_ARG, "slot recording is built without torque limits (clamp_mode 0 only)");
     if (c->ok.n > 0) return fail(MPPI_E_ARG, "slot recording is built without obstacles (remove the discs first)");
+    if (c->sk.on) return fail(MPPI_E_ARG, "slot recording is built without self collision (disable it first)");
     return chain_rollout(c, noise_dev, S_dev, nullptr, 0u, slots_dev);
 }
 
@@ -2072,6 +2403,8 @@ int mppi_chain_set_moving_obstacles(mppi_chain_ctx* c, int n, const double* disc
     }
     if (k.moving && c->move_per_cu < 1)
         return fail(MPPI_E_ARG, "obstacles: the rollout kernel with moving discs does not fit a CU");
+    if (k.moving && c->sk.on && c->self_move_per_cu < 1)
+        return fail(MPPI_E_ARG, "obstacles: the rollout kernel with moving discs and self collision does not fit a CU");
     k.dt = c->cfg.delta_t;
     k.w = cost;
     k.n = n;
@@ -2093,15 +2426,59 @@ int mppi_chain_debug_obstacle_hits(mppi_chain_ctx* c, const float* noise_dev, in
     const int blocks = (int)(((long long)K * c->lps + kCT - 1) / kCT);
     const mppi_host::Handoff& h = c->hand;
     const ChainStep* cur = c->d_step + c->cur;
-    with_rollout(c, false, true, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob) {
+    with_rollout(c, false, true, false, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob, auto) {
         if constexpr (ob && !p)   // (with_rollout also instantiates this lambda for the other kernels)
             hipLaunchKernelGGL((chain_rollout_kernel<n, p, f64, lps, false, cl, ob, true, true>), dim3(blocks), dim3(kCT), 0,
                                c->stream, c->kc, cur, c->d_dyn, noise_dev, (double*)nullptr,
                                reinterpret_cast<double*>(dir_dev), reinterpret_cast<double*>(mask_dev), h.d_counter,
                                (double*)nullptr, (double*)nullptr, (ChainStep*)nullptr, (unsigned)K, c->ex.xd, h.d_epoch,
-                               h.h_tmo.dev, c->d_runmin, (unsigned long long*)nullptr, c->ck, c->ok);
+                               h.h_tmo.dev, c->d_runmin, (unsigned long long*)nullptr, c->ck, c->ok, c->sk);
     });
     return launch_check("chain_rollout_kernel (obstacle debug)");
+}
+
+int mppi_chain_set_self_collision(mppi_chain_ctx* c, int enable, double clearance, double cost) {
+    if (!c) return fail(MPPI_E_ARG, "null context");
+    if (!(clearance >= 0.0) || isinf(clearance))
+        return fail(MPPI_E_ARG, "self collision: the clearance must be finite and >= 0");
+    if (!(cost >= 0.0) || isinf(cost)) return fail(MPPI_E_ARG, "self collision: the cost must be finite and >= 0");
+    const bool on = enable != 0 && c->n >= kSelfMinN;   // a 2-link chain has no non-adjacent pair: accepted, no effect
+    if (on && c->self_per_cu < 1) return fail(MPPI_E_ARG, "self collision: the rollout kernel with it does not fit a CU");
+    if (on && c->ok.moving && c->self_move_per_cu < 1)
+        return fail(MPPI_E_ARG, "self collision: the rollout kernel with it and moving discs does not fit a CU");
+    ChainSelfK k{};
+    k.d2d = clearance * clearance;
+    k.d2 = (float)k.d2d;   // rounded once, from the fp64 product
+    k.w = cost;
+    k.on = on ? 1 : 0;
+    c->sk = k;   // read by the next launch of any kind (a kernel argument, by value): no device call
+    return MPPI_OK;
+}
+
+int mppi_chain_debug_self_hits(mppi_chain_ctx* c, const float* noise_dev, int K, unsigned* mask_dev, float* dir_dev) {
+    if (!c || !noise_dev || !mask_dev || !dir_dev || K < 1 || K > c->cfg.K_local) return fail(MPPI_E_ARG, "bad argument");
+    // every form writes each of the first K samples' masks once, so only a chain without pairs needs the zeroes
+    HIP_TRY(hipMemsetAsync(mask_dev, 0, (size_t)K * c->cfg.T * sizeof(unsigned), c->stream));
+    if (c->n < kSelfMinN) {   // no pairs, no kernel: no bit is ever set, and the directions stay zero
+        HIP_TRY(hipMemsetAsync(dir_dev, 0, (size_t)K * c->cfg.T * 2 * c->n * sizeof(float), c->stream));
+        return MPPI_OK;
+    }
+    if (c->self_per_cu < 1) return fail(MPPI_E_ARG, "self collision: the rollout kernel with it does not fit a CU");
+    // the context's own form of the SELF kernel with the clearance in effect, discs at rest skipped (the recording
+    // instances run no disc test), counter hand-off (it ends before any hand-off), over the workgroups that hold the
+    // first K samples; the masks travel in gslab's place, the directions in slab's and K in flags'
+    const int blocks = (int)(((long long)K * c->lps + kCT - 1) / kCT);
+    const mppi_host::Handoff& h = c->hand;
+    const ChainStep* cur = c->d_step + c->cur;
+    with_rollout(c, false, true, true, [&](auto n, auto p, auto f64, auto lps, auto cl, auto ob, auto sf) {
+        if constexpr (sf && !p)
+            hipLaunchKernelGGL((chain_rollout_kernel<n, p, f64, lps, false, cl, ob, false, false, true, true>), dim3(blocks),
+                               dim3(kCT), 0, c->stream, c->kc, cur, c->d_dyn, noise_dev, (double*)nullptr,
+                               reinterpret_cast<double*>(dir_dev), reinterpret_cast<double*>(mask_dev), h.d_counter,
+                               (double*)nullptr, (double*)nullptr, (ChainStep*)nullptr, (unsigned)K, c->ex.xd, h.d_epoch,
+                               h.h_tmo.dev, c->d_runmin, (unsigned long long*)nullptr, c->ck, c->ok, c->sk);
+    });
+    return launch_check("chain_rollout_kernel (self-collision debug)");
 }
 
 

@@ -1,0 +1,214 @@
+"""CPU: the self-collision cost of the n-link chain (a cost on non-adjacent link pairs).
+
+  * tests/selfcol.py's fp64 predicate, the yardstick of the GPU tests, against a brute-force segment distance (each
+    segment sampled at 2001 points; agreement to the sampling step) on random poses and on hand-made crossing,
+    touching-at-an-end and parallel-overlapping pairs;
+  * the pair enumeration at n = 3, 4, 7 (1, 3 and 15 pairs) and the empty mask at n = 2;
+  * its penalty loop with the self cost 0 is oracle/chain_oracle.py's rollout cost, bit for bit, with and without discs;
+  * the C ABI: both entry points declared in the header and bound by _native;
+  * ChainEngine.check_self_collision and the drop-in's by-value key.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import chain_oracle as CO
+import selfcol as SC
+from conftest import ROOT
+from mppi_robotarm_amd import _native as N
+from mppi_robotarm_amd.chain import ChainEngine, ChainMPPIController, ChainParams
+
+HEADER = os.path.join(ROOT, "include", "mppi_rocm.h")
+M = 2001
+
+
+def _uniform(n, reach=2.0):
+    L = reach / n
+    return CO.ChainParams(m=(1.0,) * n, l=(L,) * n, lc=(L / 2,) * n, I=(L * L / 12.0,) * n, fk=(L,) * n, J=(0.1,) * n,
+                          b=(1.0,) * n)
+
+
+def _segments(q, fk):
+    th = np.cumsum(q)
+    jx, jy = SC.joints(np.cos(th), np.sin(th), fk)
+    return [((jx[a], jy[a]), (jx[a + 1], jy[a + 1])) for a in range(len(q))]
+
+
+def _brute_cross(p0, p1, q0, q1):
+    """Proper crossing by solving the two line equations: both parameters strictly inside (0, 1)."""
+    p0, p1, q0, q1 = (np.asarray(v, dtype=np.float64) for v in (p0, p1, q0, q1))
+    r, s = p1 - p0, q1 - q0
+    den = r[0] * s[1] - r[1] * s[0]
+    if den == 0.0:
+        return False
+    t = ((q0 - p0)[0] * s[1] - (q0 - p0)[1] * s[0]) / den
+    u = ((q0 - p0)[0] * r[1] - (q0 - p0)[1] * r[0]) / den
+    return 0.0 < t < 1.0 and 0.0 < u < 1.0
+
+
+@pytest.mark.parametrize("n", [3, 4, 7])
+def test_predicate_against_brute_force_on_random_poses(n):
+    rng = np.random.default_rng(7 + n)
+    fk = rng.uniform(0.15, 0.45, n)
+    crossed = apart = 0
+    for it in range({3: 40, 4: 20, 7: 4}[n]):                # 40 to 60 pairs per chain
+        # any pose, alternating with one that coils in one direction (random poses of a short chain seldom cross)
+        bend = rng.normal(0.0, 1.6, n - 1) if it % 2 else rng.uniform(1.2, 2.9, n - 1)
+        q = np.concatenate([[rng.uniform(-np.pi, np.pi)], bend])
+        th = np.cumsum(q)
+        e, x, _ = SC.self_test(np.cos(th), np.sin(th), fk)
+        seg = _segments(q, fk)
+        for i, (a, b) in enumerate(SC.pairs(n)):
+            brute = SC.brute_distance(*seg[a], *seg[b], m=M)
+            step = max(fk[a], fk[b]) / (M - 1)
+            want_x = _brute_cross(*seg[a], *seg[b])
+            assert bool(x[i]) == want_x, (q, a, b)
+            if want_x:
+                crossed += 1
+                assert brute <= step                   # crossing segments touch
+            else:
+                apart += 1
+                assert abs(brute - e[i]) <= step, (q, a, b, brute, e[i])
+    assert crossed >= 3 and apart >= 3                 # both cases were drawn
+
+
+def test_hand_made_pairs():
+    fk = np.array([1.0, 0.5, 1.0])
+    pi = np.pi
+    # link 2 comes back across link 0: up 1, right 0.5, then down-left through the first link
+    q = np.array([pi / 2, -pi / 2, -3 * pi / 4])
+    th = np.cumsum(q)
+    e, x, m = SC.self_test(np.cos(th), np.sin(th), fk, 0.0)
+    assert x[0] and m == 1
+    assert SC.brute_distance(*_segments(q, fk)[0], *_segments(q, fk)[2]) < 1e-3
+    # touching at an end (exact direction values, so nothing is left to rounding): link 2 comes straight back down
+    # link 1 and ends on the far end of link 0; an end on the other's line is on neither side: not a proper crossing
+    fk = np.array([4.0, 3.0, 3.0])
+    c, s = np.array([1.0, 0.0, 0.0]), np.array([0.0, 1.0, -1.0])
+    e, x, m0 = SC.self_test(c, s, fk, 0.0)
+    assert e[0] == 0.0 and not x[0] and m0 == 0        # d = 0 counts crossings only
+    assert SC.self_test(c, s, fk, 1e-9)[2] == 1        # any clearance catches the touch
+    # ... and ends in the interior of link 0 when link 1 leans back over it (a 3-4-5 triangle)
+    fk = np.array([4.0, 5.0, 4.0])
+    c, s = np.array([1.0, -0.6, 0.0]), np.array([0.0, 0.8, -1.0])
+    e, x, m0 = SC.self_test(c, s, fk, 0.0)
+    assert e[0] == 0.0 and not x[0] and m0 == 0
+    e, x, m0 = SC.self_test(c, s, fk + np.array([0.0, 0.0, 0.5]), 0.0)
+    assert x[0] and m0 == 1                            # half a metre longer, it goes through
+    # parallel, overlapping: link 2 runs back beside link 0 at distance 0.25
+    fk = np.array([1.0, 0.25, 0.8])
+    c, s = np.array([1.0, 0.0, -1.0]), np.array([0.0, 1.0, 0.0])
+    e, x, m = SC.self_test(c, s, fk, 0.25)
+    assert e[0] == 0.25 and not x[0] and m == 0        # e < d is strict
+    assert SC.self_test(c, s, fk, 0.2500001)[2] == 1
+    jx, jy = SC.joints(c, s, fk)
+    assert abs(SC.brute_distance((jx[0], jy[0]), (jx[1], jy[1]), (jx[2], jy[2]), (jx[3], jy[3])) - 0.25) < 1e-3
+
+
+def test_pair_enumeration():
+    assert SC.pairs(3) == [(0, 2)]
+    assert SC.pairs(4) == [(0, 2), (0, 3), (1, 3)]
+    p7 = SC.pairs(7)
+    assert len(p7) == 15 and p7[:5] == [(0, 2), (0, 3), (0, 4), (0, 5), (0, 6)] and p7[5] == (1, 3) and p7[-1] == (4, 6)
+    assert SC.pairs(2) == []
+    # a tight coil sets every bit, and only the 15
+    q = np.array([0.3] + [2.0 * np.pi / 3.0 * 0.99] * 6)
+    th = np.cumsum(q)
+    _, _, m = SC.self_test(np.cos(th), np.sin(th), [2.0 / 7.0] * 7, 0.5)
+    assert m == (1 << 15) - 1
+
+
+def test_two_links_have_no_pair():
+    rng = np.random.default_rng(0)
+    th = rng.uniform(-3, 3, (50, 2))
+    e, x, m = SC.self_test(np.cos(th), np.sin(th), [1.0, 1.0], 10.0)
+    assert e.shape == (50, 0) and x.shape == (50, 0) and not m.any() and m.dtype == np.uint32
+
+
+@pytest.mark.parametrize("with_discs", [False, True])
+def test_penalty_loop_with_zero_self_cost_is_the_oracles_rollout(with_discs, paths):
+    n, K, T = 4, 40, 7
+    P = _uniform(n)
+    rng = np.random.default_rng(3)
+    q = np.array([1.4] + [1.55] * (n - 1))
+    x0 = np.concatenate([q, rng.normal(0, 0.2, n)])
+    u = np.tile(CO.gravity_torque(q, P), (T, 1))
+    sigma = np.diag(np.linspace(8.0, 1.0, n))
+    eps = rng.normal(size=(K, T, n)) * np.sqrt(np.diag(sigma))
+    discs = np.array([[0.3, 0.5, 0.2], [-0.2, 0.6, 0.1]]) if with_discs else None
+    args = (x0, u, eps, paths["xydq_circle"], 40, 0.03, 100.0, 0.98, sigma, [0.5, 0.5, 5.0, 5.0], [5.0, 5.0, 50.0, 50.0])
+    want = CO.chain_rollout_costs(*args, 0.0, P, discs=discs, obstacle_cost=1.0e4, details=True)
+    got = SC.rollout_costs(P, *args, discs=discs, obstacle_cost=1.0e4, clearance=0.05, self_cost=0.0)
+    assert np.array_equal(got["S"], want["S"]) and np.array_equal(got["S_track"], want["S_track"])
+    assert np.array_equal(got["hits_disc"], want["hits"])
+    if with_discs:
+        assert want["hits"].any()
+    # and with a cost: S_track untouched, S = S_track + both penalties to rounding, the counts from the flags
+    r = SC.rollout_costs(P, *args, discs=discs, obstacle_cost=1.0e4, clearance=0.3, self_cost=7.0)
+    assert np.array_equal(r["S_track"], want["S_track"])
+    assert np.array_equal(r["hits_self"], r["flag_self"].sum(1) + r["flag_self"][:, -1])
+    assert r["hits_self"].any() and r["hits_self"].max() <= T + 1
+    np.testing.assert_allclose(r["S"], r["S_track"] + 1.0e4 * r["hits_disc"] + 7.0 * r["hits_self"], rtol=1e-13)
+    sub = SC.rollout_costs(P, *args, discs=discs, obstacle_cost=1.0e4, clearance=0.3, self_cost=7.0,
+                           hits=(None, np.zeros(K, dtype=int)))
+    np.testing.assert_allclose(sub["S"], want["S"], rtol=1e-15)
+
+
+def test_the_c_abi_is_declared_and_bound():
+    text = open(HEADER).read()
+    assert re.search(r"int\s+mppi_chain_set_self_collision\(mppi_chain_ctx\s*\*ctx,\s*int enable,\s*double clearance,"
+                     r"\s*double cost\);", text)
+    assert re.search(r"int\s+mppi_chain_debug_self_hits\(mppi_chain_ctx\s*\*ctx,\s*const float\s*\*noise_dev,\s*int K,"
+                     r"\s*unsigned\s*\*mask_dev,\s*float\s*\*dir_dev\);", text)
+    for name in ("mppi_chain_set_self_collision", "mppi_chain_debug_self_hits"):
+        assert name in N.EXPORTS
+
+
+def test_check_self_collision():
+    chk = ChainEngine.check_self_collision
+    assert chk(None, 1.0e10) == (None, 1.0e10)
+    assert chk(0, 0) == (0.0, 0.0) and chk(0.03, 7) == (0.03, 7.0)
+    assert chk(np.float32(0.5), np.int64(3)) == (0.5, 3.0)
+    nan, inf = float("nan"), float("inf")
+    for d, w in ((nan, 1.0), (-1e-9, 1.0), (inf, 1.0), (0.03, nan), (0.03, -1.0), (0.03, inf), (None, nan), (None, -1.0),
+                 ("x", 1.0), (0.03, None), ([0.1, 0.2], 1.0)):
+        with pytest.raises(ValueError):
+            chk(d, w)
+
+
+def test_the_controllers_by_value_key(paths):
+    kw = dict(delta_t=0.03, ref_path=paths["xydq_circle"], horizon_step_T=7, number_of_samples_K=64)
+    c = ChainMPPIController(**kw)
+    assert c.self_clearance is None and c.self_collision_cost == 1.0e10 and c._self_key() == (None, 1.0e10)
+    c = ChainMPPIController(**kw, self_clearance=0.03, self_collision_cost=5.0)
+    assert c._self_key() == (0.03, 5.0)
+    c.self_clearance = np.float64(0.05)                # a rebind is seen by value
+    assert c._self_key() == (0.05, 5.0)
+    c.self_clearance = None
+    assert c._self_key() == (None, 5.0)
+    with pytest.raises(ValueError):
+        ChainMPPIController(**kw, self_clearance=-0.1)
+    c.self_collision_cost = float("inf")
+    u_before, state = c.u_prev.copy(), np.random.get_state()
+    with pytest.raises(ValueError):
+        c.calc_control_input(np.zeros(14))             # before anything is drawn or moved, and before any device call
+    assert np.array_equal(c.u_prev, u_before)
+    assert all(np.array_equal(a, b) for a, b in zip(state, np.random.get_state()))
+
+    class Eng:                                         # what _push_self_collision reads and calls
+        self_clearance, self_collision_cost, calls = None, 0.0, 0
+
+        def set_self_collision(self, d, w):
+            self.self_clearance, self.self_collision_cost, self.calls = d, w, self.calls + 1
+
+    e = Eng()
+    c._push_self_collision(e, (None, 3.0))             # off stays off
+    assert e.calls == 0
+    c._push_self_collision(e, (0.03, 3.0))
+    c._push_self_collision(e, (0.03, 3.0))             # held already
+    assert e.calls == 1 and (e.self_clearance, e.self_collision_cost) == (0.03, 3.0)
+    c._push_self_collision(e, (0.03, 4.0))
+    c._push_self_collision(e, (None, 4.0))
+    assert e.calls == 3 and e.self_clearance is None

@@ -1,0 +1,652 @@
+"""GPU: the self-collision cost of the n-link chain (mppi_chain_set_self_collision; the SELF instantiations of
+chain_rollout_kernel in its three forms: fp32 with one lane per sample, fp32 with a quad per sample, fp64).
+
+Yardstick: tests/selfcol.py, the fp64 predicate and its penalty on oracle/chain_oracle.py's model through
+O.horizon_loop's hook (pinned by test_chain_self_collision_cpu.py).  Modelled on test_gpu_chain_obstacles.py, whose
+constants and helpers it uses: S 5e-5, weights 1e-10, nominal 1e-4, hit-count agreement >= 0.99, EDGE_CAP 0.05.
+
+Shapes, the smallest at which each form can go wrong: n in {3, 4, 7} (one pair, with the quad's pad link; an even chain;
+config 5's); n = 2 is the no-op.  T = 7; K = 300 at one lane per sample and in fp64, K = 100 with a quad per sample;
+dt = 0.03 s, the chain tests' Sigma, uniform links of 2 m reach.
+
+Start poses q = [1.4, phi, ..., phi], a gravity-holding nominal plus noise.  Coil poses for the masks: phi =
+0.99 * 2 pi / m for every m = 3 .. n (the chain wound into an m-gon that just fails to close, so links m apart run
+beside and through each other).  Open poses for the weights: phi = 2.08 (n = 3), 1.55 (n = 4), 0.86 (n = 7); their
+clearance is the 25th percentile of the final states' smallest pair distance in the reference's own unobstructed
+rollout, rounded to a millimetre: never taken from the kernels.
+
+The flag is a discontinuity: a device state within rounding of a boundary may fall on either side.  Nothing is excluded
+for that.  The masks are compared with the fp64 predicate on the device's OWN directions, a bit allowed to differ only
+within EDGE of a boundary (|e - d| <= EDGE, or e <= EDGE where a crossing decides); the penalty is checked exactly
+through S = (S_free + w_d hits_d) + w_s hits_s with the device's own hit counts; and the yardstick takes the device's
+hit counts where a weight depends on them.
+
+EDGE, from the device forms' rounding count (not from what the kernels give).  Every magnitude is bounded by the reach.
+The test of joint j against link L subtracts two joint positions, each a prefix sum of fk (cos, sin) with one fma per
+link and component before it: at most n roundings each, 2 n together (one lane per sample: exactly that; the quad's scan
+rounds at the magnitude of a link pair; the fp64 form rounds at 2^-53 and is compared on directions returned in fp32,
+at most 2^-25 per component and link, half a rounding); the subtraction rounds once per component (2).  From there the
+distance takes seg_hits' five roundings (two in the projection, one in each offset component, two in the sum of
+squares) and d^2 is rounded once (6); the perpendicular offset whose sign decides a crossing takes two of its own, on
+the same r, fewer than the distance's.  Each counts as 2^-24 at magnitude <= reach:
+EDGE(n) = (8 + 2 n) 2^-24 reach, 2.6e-6 m at n = 7.  The directions need not be unit vectors to that accuracy: the
+device's form is the yardstick's (the offset from the clipped foot point), on the same (cos, sin).
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+import chain_oracle as CO  # noqa: E402
+import mppi_oracle as O  # noqa: E402
+import selfcol as SC  # noqa: E402
+from conftest import STEP_FIXTURES, load_step  # noqa: E402
+from helpers import _inside, _urel  # noqa: E402
+from test_gpu_chain_obstacles import (ALPHA, DT, EDGE_CAP, FORM_IDS, FORMS, REACH, S_TOL, TW, U_TOL, W, W_TOL, T,  # noqa: E402
+                                      _chains, _engine, _hits_from_masks, _S, _sigma, place_discs)
+
+NS = [3, 4, 7]
+OPEN = {3: 2.08, 4: 1.55, 7: 0.86}
+COIL_D = (0.03, 0.0)
+COSTS = (1.0e10, 3.0e6, 7.0)        # integer-valued: w * hits is exact
+DISC_COST = 3.0e6
+LAM_COST = [(100.0, 1.0e10), (3.0e6, 3.0e6)]   # (lambda, self-collision cost) of the weight comparisons
+D_STEP = 0.004                      # the clearance of their second launch: 4 mm wider
+
+
+def edge(n):
+    return (8 + 2 * n) * 2.0 ** -24 * REACH
+
+
+def coil(m):
+    return 0.99 * 2.0 * np.pi / m
+
+
+# ---------------------------------------------------------------- the shared problems
+
+_prob = {}
+
+
+def _args(p, n, paths, lam):
+    return (_chains(n)[1], p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW)
+
+
+def _ref(p, n, paths, lam=100.0, **kw):
+    return SC.rollout_costs(*_args(p, n, paths, lam), **kw)
+
+
+def _near_edge(e, x, d, E):
+    """Entries of (K, T, P) within EDGE of a boundary: of the clearance, or of touching (where a crossing decides)."""
+    return (np.abs(e - d) <= E) | (e <= E)
+
+
+def _build(n, K, phi, draw, paths):
+    """Start state q = [1.4, phi, ...] with joint rates N(0, 0.2), a gravity-holding nominal plus noise, host noise
+    N(0, Sigma) in fp32, and the yardstick's rollout on it without any cost (the states, e and x of every pair)."""
+    from mppi_robotarm_amd.chain import gravity_torque
+    rng = np.random.default_rng(100 * n + K + int(1000 * phi) + 7919 * draw)
+    P, _ = _chains(n)
+    q = np.array([1.4] + [phi] * (n - 1))
+    x0 = np.concatenate([q, rng.normal(0, 0.2, n)])
+    sd = np.sqrt(np.diag(_sigma(n)))
+    u = np.tile(gravity_torque(q, P), (T, 1)) + rng.normal(0, 0.3, (T, n))
+    eps = (rng.normal(size=(K, T, n)) * sd).astype(np.float32).astype(np.float64)
+    p = dict(x0=x0, u=u, eps=eps)
+    p["free"] = _ref(p, n, paths, clearance=0.0)               # e, x of every state; no cost
+    return p
+
+
+def clearance_of(free):
+    """The 25th percentile of the final states' smallest pair distance, rounded to a millimetre."""
+    return round(float(np.percentile(free["e"][:, -1].min(-1), 25.0)), 3)
+
+
+def _coils_fail(ps, n):
+    """Why the coil problems cannot carry the mask comparison (None: they can), on the fp64 reference: over the poses,
+    with d = 0.03 and d = 0 together, every pair's bit is set in some state and clear in some state, every pair
+    crosses in some state, and at most EDGE_CAP of the entries lie within EDGE of a boundary."""
+    e = np.concatenate([p["free"]["e"] for _, p in ps], 1)                 # (K, poses * T, P)
+    x = np.concatenate([p["free"]["x"] for _, p in ps], 1)
+    for i, pair in enumerate(SC.pairs(n)):
+        bits = np.concatenate([(x[..., i] | (e[..., i] < d)).ravel() for d in COIL_D])
+        if not bits.any() or bits.all():
+            return f"the bit of pair {pair} is {'always' if bits.all() else 'never'} set"
+        if not x[..., i].any():
+            return f"pair {pair} never crosses"
+    for d in COIL_D:
+        if float(np.mean(_near_edge(e, x, d, edge(n)))) > EDGE_CAP:
+            return f"too many entries within EDGE of a boundary at d = {d}"
+    return None
+
+
+def _open_fail(p, n):
+    """Why the open problem cannot carry the weight comparisons (None: it can), on the fp64 reference: with the
+    clearance of its own unobstructed rollout, 10-90 % of the samples self-collide at some step, and at most EDGE_CAP
+    of the entries lie within EDGE of a boundary."""
+    free, d = p["free"], clearance_of(p["free"])
+    if not np.all(np.isfinite(free["S"])) or d <= 0.0:
+        return "a rollout diverges, or the clearance rounds to 0"
+    share = float(np.mean((free["x"] | (free["e"] < d)).any((1, 2))))
+    if not 0.10 <= share <= 0.90:
+        return f"{share:.0%} of the samples self-collide"
+    if float(np.mean(_near_edge(free["e"], free["x"], d, edge(n)))) > EDGE_CAP:
+        return "too many entries within EDGE of a boundary"
+    return None
+
+
+def _weights_fail(p, n, paths):
+    """Why the open problem cannot carry the comparison of the weighted noise at U_TOL (None: it can), on the fp64
+    reference.  These poses lie far from the path, S is ~1e5 .. 1e7, and at lambda = 100 a rounding of S is a visible
+    step of a weight: where two samples nearly tie for the minimum, the fp32 rollouts' S (T steps of a few 2^-24
+    roundings each: 2^-20 relative) moves w_eps by more than the tolerance, whatever the self-collision cost does.
+    So the yardstick's own w_eps must stay within U_TOL / 4 when its S is perturbed by 2^-20 relative (four fixed
+    draws of the perturbation), at both (lambda, cost) settings and both clearances of the comparison, and on the
+    torque-limited problem of test 5, whose clearance must also leave 10-90 % of its samples colliding."""
+    rng = np.random.default_rng(n)
+    d0 = clearance_of(p["free"])
+    lo, hi = _torque_limits(p, n)
+    clamped = _ref(p, n, paths, lo=lo, hi=hi, clearance=0.0)
+    dc = clearance_of(clamped)
+    share = float(np.mean((clamped["x"] | (clamped["e"] < dc)).any((1, 2))))
+    if dc <= 0.0 or not 0.10 <= share <= 0.90:
+        return f"with torque limits {share:.0%} of the samples self-collide"
+    cases = [(lam, w, d, None, None) for lam, w in LAM_COST for d in (d0, d0 + D_STEP)] + [(100.0, 1.0e10, dc, lo, hi)]
+    for lam, w, d, a, b in cases:
+        r = SC.step(*_args(p, n, paths, lam), lo=a, hi=b, clearance=d, self_cost=w)
+        for _ in range(4):
+            Sp = r["S"] * (1.0 + 2.0 ** -20 * rng.uniform(-1.0, 1.0, r["S"].shape))
+            moved = _urel(O.weighted_noise(O.compute_weights(Sp, lam), p["eps"]), r["w_eps_raw"])
+            if moved > U_TOL / 4:
+                return f"w_eps moves {moved:.1e} under a 2^-20 perturbation of S at lambda {lam}"
+    return None
+
+
+def _torque_limits(p, n):
+    sd = np.sqrt(np.diag(_sigma(n)))
+    return p["u"][0] - 0.5 * sd, p["u"][0] + 0.8 * sd
+
+
+def _problems(n, K, paths):
+    """The problems of (n, K): the coil poses and the open pose with its clearance, computed once, shared, never
+    modified.  The start rates and the nominal's noise move all samples of a problem together, so one draw of them may
+    carry every sample into collision or none: the draw is the first of eight (by the fp64 yardstick alone, nothing of
+    the kernels) on which the preconditions of every comparison below hold; they are asserted on what is returned: a
+    test that cannot fail must not pass."""
+    if (n, K) not in _prob:
+        for draw in range(8):
+            ps = [(m, _build(n, K, coil(m), draw, paths)) for m in range(3, n + 1)]
+            op = _build(n, K, OPEN[n], draw, paths)
+            if _coils_fail(ps, n) is None and _open_fail(op, n) is None and _weights_fail(op, n, paths) is None:
+                break
+        assert _coils_fail(ps, n) is None, _coils_fail(ps, n)
+        assert _open_fail(op, n) is None, _open_fail(op, n)
+        assert _weights_fail(op, n, paths) is None, _weights_fail(op, n, paths)
+        op["d"] = clearance_of(op["free"])
+        _prob[(n, K)] = (ps, op)
+    return _prob[(n, K)]
+
+
+def _coils(n, K, paths):
+    return _problems(n, K, paths)[0]
+
+
+def _open(n, K, paths):
+    return _problems(n, K, paths)[1]
+
+
+def _stage(eng, p, paths):
+    eng.set_step_inputs(p["x0"], paths["xydq_circle"][40:70], p["u"])
+    return eng.upload_noise(p["eps"])
+
+
+def _self_hits(eng, noise):
+    mask, _ = eng.self_hits(noise)
+    return _hits_from_masks(mask)
+
+
+def _disc_hits(eng, noise):
+    mask, _ = eng.obstacle_hits(noise)
+    return _hits_from_masks(mask)
+
+
+# ---------------------------------------------------------------- 1: mask parity on the device's own directions
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_mask_parity_on_the_devices_own_directions(precision, lps, K, n, paths):
+    fk = _chains(n)[1].fk
+    E = edge(n)
+    P = len(SC.pairs(n))
+    bit = np.uint32(1) << np.arange(P, dtype=np.uint32)
+    eng = _engine(n, K, precision=precision, lps=lps)
+    seen_set, seen_clear = np.zeros(P, bool), np.zeros(P, bool)
+    for m, p in _coils(n, K, paths):
+        noise = _stage(eng, p, paths)
+        th = np.cumsum(p["free"]["q"], -1)
+        for d in COIL_D:
+            eng.set_self_collision(d, 1.0e10)
+            mask, dirs = eng.self_hits(noise)
+            assert mask.shape == (K, T) and mask.dtype == np.uint32 and dirs.shape == (K, T, 2 * n)
+            assert float(np.max(np.abs(dirs - np.concatenate([np.cos(th), np.sin(th)], -1)))) < 1e-4
+            e, x, want = SC.self_test(dirs[..., :n], dirs[..., n:], fk, d)
+            differ = ((mask[..., None] ^ want[..., None]) & bit) != 0             # (K, T, P)
+            near = _near_edge(e, x, d, E)
+            worst = float(np.minimum(np.abs(e - d), e)[differ].max()) if differ.any() else 0.0
+            print(f"{precision} lps {lps} n {n} coil {m} d {d}: {float(np.mean(mask != 0)):.1%} of the states "
+                  f"self-collide, {int(differ.sum())} bits differ (farthest from a boundary {worst:.2e} m, EDGE {E:.2e} m)")
+            assert not np.any(differ & ~near), f"a bit differs {worst:.2e} m from a boundary"
+            assert float(np.mean(differ)) <= EDGE_CAP
+            assert not np.any(mask >> np.uint32(P))                               # bits of pairs that do not exist
+            got = (mask[..., None] & bit) != 0
+            seen_set |= got.any((0, 1))
+            seen_clear |= (~got).any((0, 1))
+    eng.close()
+    assert seen_set.all() and seen_clear.all()                                    # every pair is exercised
+
+
+# ---------------------------------------------------------------- 2: the decomposition, bit for bit
+
+@pytest.mark.parametrize("lam", [100.0, 3.0e6])
+@pytest.mark.parametrize("handoff", ["poll", "counter"])
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_S_is_the_free_S_plus_both_penalties_bit_for_bit(precision, lps, K, n, handoff, lam, paths, monkeypatch):
+    """S of a launch with the feature is the S of the same context's launch without it, through the CLAMP kernel on
+    +-1e30 limits, plus w_s hits_s with the hits rebuilt from the debug masks; with three discs as well,
+    (S_free + w_d hits_d) + w_s hits_s: one fp64 rounding each, the products exact."""
+    if handoff == "counter":
+        monkeypatch.setenv("MPPI_HANDOFF", "counter")
+    else:
+        monkeypatch.delenv("MPPI_HANDOFF", raising=False)
+    p = _open(n, K, paths)
+    eng = _engine(n, K, lam, precision, lps, u_min=-1e30, u_max=1e30)
+    assert eng.handoff == handoff
+    noise = _stage(eng, p, paths)
+    S_free = _S(eng, noise)
+    w_free = eng.weighted_noise()
+    assert np.all(np.isfinite(S_free))
+    discs = place_discs(p["free"], _chains(n)[1])[:3]
+    for w in COSTS:
+        eng.set_self_collision(p["d"], w)
+        assert eng.self_clearance == p["d"] and eng.self_collision_cost == w
+        S = _S(eng, noise)
+        hs = _self_hits(eng, noise)
+        assert hs.max() <= T + 1 and hs.any() and not np.all(hs > 0)       # (10-90 % on the reference: _open_fail)
+        assert np.array_equal(S, S_free + w * hs.astype(np.float64)), w
+        wk = np.exp(-(S - S.min()) / lam)
+        np.testing.assert_allclose(eng.weighted_noise(), np.einsum("k,ktd->td", wk / wk.sum(), p["eps"]),
+                                   rtol=W_TOL, atol=W_TOL)
+        eng.set_obstacles(discs, DISC_COST)
+        S = _S(eng, noise)
+        hd = _disc_hits(eng, noise)
+        assert hd.any() and np.array_equal(_self_hits(eng, noise), hs)
+        assert np.array_equal(S, (S_free + DISC_COST * hd.astype(np.float64)) + w * hs.astype(np.float64)), w
+        eng.set_obstacles(None)
+    eng.set_self_collision(None)
+    assert eng.self_clearance is None
+    assert np.array_equal(_S(eng, noise), S_free) and np.array_equal(eng.weighted_noise(), w_free)
+    eng.close()
+
+
+# ---------------------------------------------------------------- 3: no limits is wide limits
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_no_limits_is_wide_limits_bit_for_bit(precision, lps, K, n, paths):
+    """The SELF kernels are built with the clamp only: without torque limits they run on -+inf limits, which must give
+    the bits of +-1e30 limits in S, w_eps and the fused update's nominal."""
+    p = _open(n, K, paths)
+    got = []
+    for lim in (None, 1e30):
+        eng = _engine(n, K, 3.0e6, precision, lps, **({} if lim is None else dict(u_min=-lim, u_max=lim)))
+        noise = _stage(eng, p, paths)
+        eng.set_self_collision(p["d"], 3.0e6)
+        S = _S(eng, noise, fused_update=True)
+        got.append((S, eng.weighted_noise(), eng.nominal()))
+        eng.close()
+    for a, b in zip(*got):
+        assert np.all(np.isfinite(a)) and np.array_equal(a, b)
+    assert np.any(got[0][0] >= 3.0e6)
+
+
+# ---------------------------------------------------------------- 4: weighted noise and the nominal
+
+@pytest.mark.parametrize("lam,w", LAM_COST)
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_weighted_noise_and_nominal(precision, lps, K, n, lam, w, paths):
+    p = _open(n, K, paths)
+    eng = _engine(n, K, lam, precision, lps)
+    noise = _stage(eng, p, paths)
+    seen = []
+    for d in (p["d"], p["d"] + D_STEP):                       # the clearance changed between two launches
+        eng.set_step_inputs(p["x0"], paths["xydq_circle"][40:70], p["u"])
+        eng.set_self_collision(d, w)
+        S, weps = _S(eng, noise), eng.weighted_noise()
+        hs = _self_hits(eng, noise)
+        seen.append(hs)
+        r = SC.step(*_args(p, n, paths, lam), clearance=d, self_cost=w, hits=(None, hs))
+        assert float(np.mean(hs == r["hits_self"])) >= 0.99
+        host = O.weighted_noise(O.compute_weights(S, lam), p["eps"])
+        srel = float(np.max(np.abs(S - r["S"]) / np.abs(r["S"])))
+        print(f"{precision} lps {lps} n {n} lam {lam} d {d}: S rel {srel:.2e}, w_eps vs host sum "
+              f"{float(np.max(np.abs(weps - host))):.2e}, vs yardstick {_urel(weps, r['w_eps_raw']):.2e}")
+        assert srel < S_TOL
+        np.testing.assert_allclose(weps, host, rtol=W_TOL, atol=W_TOL)
+        assert _urel(weps, r["w_eps_raw"]) < U_TOL
+        eng.rollout(noise, fused_update=True)                 # the fused update, from the same nominal
+        assert _urel(eng.nominal(), r["u_seq"]) < U_TOL
+    assert not np.array_equal(seen[0], seen[1])               # the second launch saw the change
+    assert seen[1].sum() > seen[0].sum()
+    eng.close()
+
+
+# ---------------------------------------------------------------- 5: with torque limits
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_decomposition_with_torque_limits(precision, lps, K, n, paths):
+    """Real limits (clamp_mode 2): the decomposition against the same context's clamped launch without the feature, the
+    hit counts against the yardstick's with limits, and the fused update's nominal inside the limits."""
+    p = _open(n, K, paths)
+    lo, hi = _torque_limits(p, n)
+    w = 1.0e10
+    eng = _engine(n, K, 100.0, precision, lps, u_min=lo, u_max=hi)
+    noise = _stage(eng, p, paths)
+    S_free = _S(eng, noise)
+    free = _ref(p, n, paths, lo=lo, hi=hi, clearance=0.0)
+    assert float(np.max(np.abs(S_free - free["S"]) / np.abs(free["S"]))) < S_TOL
+    # the clipped controls move the chain elsewhere: the clearance from this rollout, by the same rule
+    d = clearance_of(free)
+    share = float(np.mean((free["x"] | (free["e"] < d)).any((1, 2))))
+    assert d > 0.0 and 0.10 <= share <= 0.90, (d, share)       # on the reference
+    eng.set_self_collision(d, w)
+    S = _S(eng, noise)
+    hs = _self_hits(eng, noise)
+    assert hs.any() and not np.all(hs > 0)
+    assert np.array_equal(S, S_free + w * hs.astype(np.float64))
+    r = SC.step(*_args(p, n, paths, 100.0), lo=lo, hi=hi, clearance=d, self_cost=w, hits=(None, hs))
+    assert float(np.mean(hs == r["hits_self"])) >= 0.99
+    eng.rollout(noise, fused_update=True)
+    u = eng.nominal()
+    assert _inside(u, lo, hi)                                 # the nominal's clamp still runs (mode 2)
+    assert _urel(u, r["u_seq"]) < U_TOL
+    eng.close()
+
+
+# ---------------------------------------------------------------- 6: with a moving disc
+
+_moving = {}
+
+
+def _moving_disc(n, K, paths):
+    """(disc (1, 3), velocity (1, 2)): one of place_discs' discs that crosses its own radius over the horizon and is
+    where the static layout has it at the end of it; the first disc and direction (of eight each) on which, by the
+    fp64 yardstick alone, the motion changes the hit count of >= 10 % of the samples and 10-90 % of them collide (a
+    coiled chain leaves little room: many a disc beside one link lies across another)."""
+    if (n, K) not in _moving:
+        p = _open(n, K, paths)
+        for d0 in place_discs(p["free"], _chains(n)[1]):
+            for k in range(8):
+                ang = 0.4 + k * np.pi / 4
+                v = (d0[2] / (T * DT)) * np.array([[np.cos(ang), np.sin(ang)]])
+                disc = np.array([[d0[0] - v[0, 0] * T * DT, d0[1] - v[0, 1] * T * DT, d0[2]]])
+                move = _ref(p, n, paths, discs=disc, vel=v, obstacle_cost=1.0)["hits_disc"]
+                rest = _ref(p, n, paths, discs=disc, obstacle_cost=1.0)["hits_disc"]
+                if float(np.mean(move != rest)) >= 0.10 and 0.10 <= float(np.mean(move > 0)) <= 0.90:
+                    _moving[(n, K)] = (disc, v)
+                    break
+            if (n, K) in _moving:
+                break
+        assert (n, K) in _moving, "no disc of the layout whose motion matters"
+    return _moving[(n, K)]
+
+
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_decomposition_with_a_moving_disc(precision, lps, K, n, paths):
+    """A SELF + MOVE instance: one disc that arrives where the static layout has it at the end of the horizon; S
+    decomposes with both counts, and the disc's count is the yardstick's with the motion."""
+    p = _open(n, K, paths)
+    disc, v = _moving_disc(n, K, paths)
+    w = 3.0e6
+    eng = _engine(n, K, 3.0e6, precision, lps, u_min=-1e30, u_max=1e30)
+    noise = _stage(eng, p, paths)
+    S_free = _S(eng, noise)
+    eng.set_obstacles(disc, DISC_COST, velocities=v)
+    eng.set_self_collision(p["d"], w)
+    S = _S(eng, noise)
+    hd, hs = _disc_hits(eng, noise), _self_hits(eng, noise)
+    assert hd.any() and hs.any()
+    assert np.array_equal(S, (S_free + DISC_COST * hd.astype(np.float64)) + w * hs.astype(np.float64))
+    r = _ref(p, n, paths, 3.0e6, discs=disc, vel=v, obstacle_cost=DISC_COST, clearance=p["d"], self_cost=w)
+    assert float(np.mean(hd == r["hits_disc"])) >= 0.99 and float(np.mean(hs == r["hits_self"])) >= 0.99
+    eng.close()
+
+
+# ---------------------------------------------------------------- 7: two shards
+
+@pytest.mark.parametrize("precision,lps,K", FORMS, ids=FORM_IDS)
+def test_two_shards_merge_to_the_unsharded_launch(precision, lps, K, paths):
+    n = 7
+    p = _open(n, K, paths)
+    lam, w = 3.0e6, 3.0e6
+    one = _engine(n, K, lam, precision, lps)
+    noise = _stage(one, p, paths)
+    one.set_self_collision(p["d"], w)
+    one.rollout(noise)
+    want = one.weighted_noise()
+    one.close()
+    Ka = K // 2 + 7
+    engines, parts = [], []
+    for off, Kl in ((0, Ka), (Ka, K - Ka)):
+        e = _engine(n, Kl, lam, precision, lps, K_total=K, k_offset=off)
+        e.set_step_inputs(p["x0"], paths["xydq_circle"][40:70], p["u"])
+        e.set_self_collision(p["d"], w)
+        nz = e.new_noise()
+        nz.copy_(noise[:, off:off + Kl])
+        part = e.new_partial()
+        e.rollout(nz, partial_out=part)
+        e.synchronize()
+        engines.append(e)
+        parts.append(part)
+    engines[1].merge(torch.cat(parts).contiguous(), 2)
+    got = engines[1].weighted_noise()
+    for e in engines:
+        e.close()
+    np.testing.assert_allclose(got, want, rtol=W_TOL, atol=W_TOL)
+    assert np.any(want != 0.0)
+
+
+# ---------------------------------------------------------------- 8: n = 2 is the no-op
+
+@pytest.mark.parametrize("name", STEP_FIXTURES)
+def test_chain_at_n2_with_the_feature_reproduces_reference_steps(name, paths):
+    """test_gpu_chain.py's comparison with the reference's golden steps, self-collision enabled: two links have no
+    non-adjacent pair, so nothing changes."""
+    from mppi_robotarm_amd.chain import ChainMPPIController, ChainParams
+    g = load_step(name)
+    c = ChainMPPIController(float(g["delta_t"]), paths[str(g["path"])], int(g["T"]), int(g["K"]),
+                            float(g["param_exploration"]), float(g["param_lambda"]), float(g["param_alpha"]),
+                            g["sigma"], g["stage_cost_weight"], g["terminal_cost_weight"],
+                            visualze_sampled_trajs="sampled_traj" in g, chain=ChainParams.from_arm2(),
+                            u_init=g["u_prev"], self_clearance=10.0, self_collision_cost=1.0e10)
+    c.prev_waypoints_idx = int(g["prev_idx"])
+    eps = g["eps"].astype(np.float64)
+    c._calc_epsilon = lambda *a, **k: eps
+    c.keep_costs = True
+    u0, u_seq, opt, samp = c.calc_control_input(g["x0"])
+    S = c.last_S
+    assert c._engine.self_clearance == 10.0 and c._engine.self_collision_cost == 1.0e10
+    assert int(np.argmin(S)) == int(np.argmin(g["S"]))
+    assert float(np.max(np.abs(S - g["S"]) / np.abs(g["S"]))) < S_TOL
+    assert _urel(u_seq, g["u_seq"]) < U_TOL
+    assert c.prev_waypoints_idx == int(g["prev_idx_after"])
+    np.testing.assert_allclose(opt, g["optimal_traj"], rtol=1e-4, atol=1e-4)
+    if "sampled_traj" in g:
+        np.testing.assert_allclose(samp, g["sampled_traj"], rtol=1e-4, atol=1e-4)
+    mask, dirs = c._engine.self_hits(c._noise_dev, K=min(64, int(g["K"])))
+    assert mask.dtype == np.uint32 and not mask.any() and dirs.shape[-1] == 4
+    c.close()
+
+
+# ---------------------------------------------------------------- 9: bad arguments
+
+def test_set_self_collision_rejects_bad_arguments(paths):
+    from mppi_robotarm_amd import _native as N
+    n, K = 7, 300
+    p = _open(n, K, paths)
+    eng = _engine(n, K, lps=1)
+    noise = _stage(eng, p, paths)
+    eng.set_self_collision(p["d"], 1.0e10)
+    S = _S(eng, noise)
+    assert np.any(S >= 1.0e10)
+    lib = eng._lib
+    nan, inf = float("nan"), float("inf")
+    for en, d, w in ((1, nan, 1.0), (1, -0.01, 1.0), (1, inf, 1.0), (1, 0.03, nan), (1, 0.03, -1.0), (1, 0.03, inf),
+                     (0, nan, 1.0), (0, 0.03, -1.0)):
+        assert lib.mppi_chain_set_self_collision(eng._ctx, en, d, w) == N.MPPI_E_ARG, (en, d, w)
+        assert b"self collision" in lib.mppi_last_error()
+    assert lib.mppi_chain_set_self_collision(None, 1, 0.03, 1.0) == N.MPPI_E_ARG
+    for d, w in ((-0.01, 1.0), (nan, 1.0), (inf, 1.0), (0.03, -1.0), (0.03, inf), (None, nan)):
+        with pytest.raises(ValueError):
+            eng.set_self_collision(d, w)
+    assert eng.self_clearance == p["d"] and eng.self_collision_cost == 1.0e10
+    assert np.array_equal(_S(eng, noise), S)                  # a rejected call keeps the setting in effect
+    with pytest.raises(ValueError):
+        eng.debug_slots(noise)                                # the slot-recording instances have no self-collision
+    for K_bad in (0, K + 1):
+        with pytest.raises(ValueError):
+            eng.self_hits(noise, K=K_bad)
+    assert lib.mppi_chain_set_self_collision(eng._ctx, 1, 0.0, 0.0) == N.MPPI_OK   # zero clearance and cost are allowed
+    assert np.all(_S(eng, noise) < 1.0e10)
+    assert lib.mppi_chain_set_self_collision(eng._ctx, 1, 10.0, 1.0) == N.MPPI_OK  # wider than the reach: every pair
+    assert np.all(eng.self_hits(noise, K=5)[0] == np.uint32(0x7FFF))
+    eng.set_self_collision(None)
+    assert eng.debug_slots(noise).shape == (K, T)
+    eng.close()
+
+
+# ---------------------------------------------------------------- 10: the drop-in
+
+@pytest.mark.parametrize("precision", ["f32", "f64", "auto"])
+def test_dropin_keeps_the_arm_off_itself(precision, paths):
+    """ChainMPPIController at n = 7, T = 16, K = 2048 over six closed-loop steps on the fp64 plant, from the open pose
+    with self_collision_cost dominating: some sampled rollouts pay it, no executed state self-collides; an in-place
+    change and self_clearance = None are seen on the next call; a bad value raises before the RNG moves.  With
+    precision="auto" the fp64 engine is forced on the third step, which builds it, and on the step after the change,
+    which finds it parked with the old clearance."""
+    from mppi_robotarm_amd.chain import CHAIN7_SIGMA, ChainMPPIController, gravity_torque
+    n = 7
+    P, Po = _chains(n)
+    path = paths["xydq_circle"]
+    q0 = np.array([1.4] + [OPEN[n]] * (n - 1))
+    x = np.concatenate([q0, np.zeros(n)])
+    _, e0, x0c, _ = SC.self_collides(q0, Po.fk, 0.0)
+    dt, T_, K_ = 0.006, 16, 2048
+    # over 16 steps of 6 ms the closest pair (9 cm apart at the start) moves by millimetres: the clearance is taken from
+    # the yardstick's own rollouts under the controller's Sigma, the 5th percentile of their closest approach rounded
+    # to 0.1 mm, so about one rollout in twenty pays and the start pose is clear of it
+    rng = np.random.default_rng(11)
+    eps = rng.normal(size=(256, T_, n)) * np.sqrt(np.diag(CHAIN7_SIGMA))
+    ug = gravity_torque(q0, P)
+    ref = SC.rollout_costs(Po, x, np.tile(ug, (T_, 1)), eps, path, 0, dt, 100.0, 0.98, CHAIN7_SIGMA, W, TW, clearance=0.0)
+    d = round(float(np.quantile(ref["e"].min((1, 2)), 0.05)), 4)
+    assert 0.03 < d < float(e0.min()) - 1e-3 and not x0c.any() and not ref["x"].any()
+    assert 0.01 <= float(np.mean(ref["e"].min((1, 2)) < d)) <= 0.50
+    np.random.seed(5)
+    c = ChainMPPIController(dt, path, T_, K_, 0.0, 100.0, 0.98, CHAIN7_SIGMA, chain=P, precision=precision, u_init=ug,
+                            self_clearance=d, self_collision_cost=1.0e10)
+    c.keep_costs = True
+    paid = 0
+    auto = precision == "auto"
+    for i in range(6):
+        if auto and i == 2:
+            c._spread = True
+        u0, _, _, _ = c.calc_control_input(x)
+        u0 = np.array(u0)
+        if not auto:
+            assert c.last_precision == precision
+        elif i == 2:
+            assert c.last_precision == "f64"
+        assert c._engine.self_clearance == d and c._engine.self_collision_cost == 1.0e10
+        paid += int(np.sum(c.last_S >= 1.0e10))
+        qn, dqn = CO.chain_forward_dynamics(x[None, :n], x[None, n:], u0[None, :], dt, Po)
+        x = np.concatenate([qn[0], dqn[0]])
+        assert not SC.self_collides(x[:n], Po.fk, d)[0]
+    assert paid > 0                                           # the cost was in reach of the sampled rollouts
+    # an in-place change: a clearance wider than the reach, every sample pays at every step
+    c.self_clearance = 10.0
+    if auto:
+        assert "f64" in set(c._slots) | {c._active}           # the fp64 engine exists, holding the old clearance
+        c._spread = True
+    c.calc_control_input(x)
+    assert np.all(c.last_S >= 17 * 1.0e10) and c._engine.self_clearance == 10.0
+    if auto:
+        assert c.last_precision == "f64" and c._active == "f64"
+    c.self_clearance = None
+    c.calc_control_input(x)
+    assert np.all(c.last_S < 1.0e10) and c._engine.self_clearance is None
+    c.self_clearance = -1.0
+    u_before, state = c.u_prev.copy(), np.random.get_state()
+    with pytest.raises(ValueError):
+        c.calc_control_input(x)
+    assert np.array_equal(c.u_prev, u_before)
+    assert all(np.array_equal(a, b) for a, b in zip(state, np.random.get_state()))
+    c.close()
+
+
+# ---------------------------------------------------------------- 11: lifetime
+
+LIFE_K, LIFE_T, LIFE_N = 65536, 128, 7
+
+
+def test_contexts_with_self_collision_return_their_memory(paths):
+    """32 create / enable / launch / self_hits / close cycles of the three forms leave the device's free memory where
+    it was, by test_gpu_lifetime.py's measure: the drop over the cycles stays below one cycle's live footprint F, and
+    F > 0 (sized as test_gpu_chain_obstacles.py's lifetime test, so that F shows)."""
+    from mppi_robotarm_amd.chain import CHAIN7_SIGMA, CHAIN7_X0, ChainEngine, ChainParams, gravity_torque
+    n, K, T_ = LIFE_N, LIFE_K, LIFE_T
+    P = ChainParams()
+    u = np.tile(gravity_torque(CHAIN7_X0[:n], P), (T_, 1))
+    noise = torch.empty((T_, K, n), dtype=torch.float32, device="cuda")
+
+    def free():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    def cycle(probe=None):
+        engines = [ChainEngine(K, T_, 0.006, 100.0, ALPHA, CHAIN7_SIGMA, W, TW, 0.0, P, device=0, precision=pr,
+                               lanes_per_sample=lps) for pr, lps, _ in FORMS]
+        for eng in engines:
+            eng.set_step_inputs(CHAIN7_X0, paths["xydq_circle"][40:70], u)
+            eng.set_self_collision(0.03, 1.0e10)
+            eng.rollout(noise, fused_update=True)
+            eng.self_hits(noise, K=16)
+            eng.synchronize()
+        if probe is not None:
+            probe()
+        for eng in engines:
+            eng.close()
+
+    first = ChainEngine(K, T_, 0.006, 100.0, ALPHA, CHAIN7_SIGMA, W, TW, 0.0, P, device=0)
+    first.philox_noise(3, 0, out=noise)
+    first.synchronize()
+    first.close()
+    cycle()
+    alive = []
+    before = free()
+    cycle(probe=lambda: alive.append(free()))
+    F = before - alive[0]
+    for _ in range(2):
+        cycle()
+    start = free()
+    for _ in range(32):
+        cycle()
+    drop = start - free()
+    print(f"lifetime: F = {F} B with one cycle's contexts alive, drop over 32 cycles = {drop} B")
+    assert F > 0
+    assert drop < F
