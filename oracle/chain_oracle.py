@@ -43,6 +43,27 @@ Workspace obstacles (discs, at rest or moving): the arm's collision cost
 state collides when any link touches any disc.  At n = 2 with
 ChainParams.from_arm2() it is the arm's definition (test_chain_obstacle_cpu.py,
 test_chain_moving_obstacle_cpu.py).
+
+Self-collision (mppi_chain_set_self_collision).  Joint j of the chain is
+b_{j-1} = sum_{i < j} fk_i (cos th_i, sin th_i) (joint 0 the origin, joint n the
+tip), link a the zero-thickness segment from joint a to joint a + 1.  For every
+pair of links a < b with b >= a + 2:
+
+  * e(a, b): the smallest of the four endpoint-to-segment distances (the ends of
+    b against a, the ends of a against b), each with the projection on the link's
+    direction clipped to [0, fk] as chain_segment_test clips it;
+  * x(a, b): the segments cross properly, the two ends of each strictly on
+    opposite sides of the other's line;
+  * the pair self-collides when x(a, b) or e(a, b) < d, d >= 0 the clearance
+    (d = 0: crossings only).
+
+A state self-collides when any pair does.  Every step of the horizon whose new
+state self-collides adds the cost to its sample's S, the final state once more,
+in the discs' one penalty (O.collision_costs' ``clearance`` and ``self_cost``):
+S = S_track + obstacle_cost hits + self_cost hits_self, each count in
+[0, T + 1].  The pairs are enumerated a ascending, then b ascending
+(chain_self_pairs); bit i of a mask (uint32) is pair i.  Pinned by
+test_chain_self_collision_cpu.py.
 """
 from __future__ import annotations
 
@@ -167,6 +188,48 @@ def chain_segment_test(c, s, discs, fk):
     return dist, clipped
 
 
+def chain_self_pairs(n):
+    """The non-adjacent link pairs in mask order: (0, 2), (0, 3), ..., (1, 3), ...: (n - 1)(n - 2) / 2 of them."""
+    return [(a, b) for a in range(n) for b in range(a + 2, n)]
+
+
+def chain_joints(c, s, fk):
+    """(jx, jy), each (..., n + 1): joint j = b_{j-1} from the direction values c, s (..., n)."""
+    c, s, fk = (np.asarray(v, dtype=np.float64) for v in (c, s, fk))
+    z = np.zeros(c.shape[:-1] + (1,))
+    return (np.concatenate([z, np.cumsum(fk * c, -1)], -1), np.concatenate([z, np.cumsum(fk * s, -1)], -1))
+
+
+def chain_self_test(c, s, fk, d=0.0):
+    """Every non-adjacent link pair from the direction values c, s (..., n): (e (..., P) fp64, x (..., P) bool,
+    mask (...) uint32) over the P = len(chain_self_pairs(n)) pairs; bit i of mask is pair i in self-collision: x or
+    e < d.  n = 2: no pairs, mask 0."""
+    c, s, fk = (np.asarray(v, dtype=np.float64) for v in (c, s, fk))
+    pairs = chain_self_pairs(c.shape[-1])
+    jx, jy = chain_joints(c, s, fk)
+
+    def point_link(j, L):
+        """(distance, signed perpendicular offset) of joint j from link L, the projection clipped to [0, fk_L]."""
+        px, py = jx[..., j] - jx[..., L], jy[..., j] - jy[..., L]
+        ux, uy = c[..., L], s[..., L]
+        pr = px * ux + py * uy
+        t = np.clip(pr, 0.0, fk[L])
+        return np.hypot(px - t * ux, py - t * uy), ux * py - uy * px
+
+    e = np.zeros(c.shape[:-1] + (len(pairs),))
+    x = np.zeros(e.shape, dtype=bool)
+    mask = np.zeros(c.shape[:-1], dtype=np.uint32)
+    for i, (a, b) in enumerate(pairs):
+        d0, s0 = point_link(b, a)                             # the ends of link b against link a
+        d1, s1 = point_link(b + 1, a)
+        d2, s2 = point_link(a, b)                             # the ends of link a against link b
+        d3, s3 = point_link(a + 1, b)
+        e[..., i] = np.minimum(np.minimum(d0, d1), np.minimum(d2, d3))
+        x[..., i] = (s0 * s1 < 0.0) & (s2 * s3 < 0.0)
+        mask |= np.where(x[..., i] | (e[..., i] < d), np.uint32(1 << i), np.uint32(0))
+    return e, x, mask
+
+
 def chain_touch_mask(dist, discs):
     """The masks of mppi_chain_debug_obstacle_hits from chain_segment_test's distances: bit 8 j + a is link a
     touching disc j (uint64, dist's shape without its last two axes)."""
@@ -188,6 +251,14 @@ def chain_collides(q, discs, P):
     return flag, O.clearance(dist, discs), dist, clipped
 
 
+def chain_self_collides(q, fk, d):
+    """(flag (...), e, x, mask) of the states q (..., n): flag where any non-adjacent pair self-collides
+    (chain_self_test at the clearance d)."""
+    th = np.cumsum(np.asarray(q, dtype=np.float64), -1)
+    e, x, mask = chain_self_test(np.cos(th), np.sin(th), fk, d)
+    return mask != 0, e, x, mask
+
+
 def chain_moving_masks(dirs, discs, vel, dt, fk, shift=0):
     """O.masks_over_horizon for the chain, dirs (K, T, 2 n) = (cos th_a at a, sin th_a at n + a): mask uint64 as
     mppi_chain_debug_obstacle_hits lays it out, gap (K, T, nd, n)."""
@@ -207,7 +278,8 @@ def chain_model(P: ChainParams = ChainParams()):
                    dot=lambda a, v: v @ a,
                    trajectory=lambda x0, controls, dt: chain_rollout_trajectory(x0, controls, dt, P),
                    collides=lambda s, discs: chain_collides(s[0], discs, P),
-                   record=lambda s: (np.stack(chain_fk(s[0], P), -1), s[0], s[1]))
+                   record=lambda s: (np.stack(chain_fk(s[0], P), -1), s[0], s[1]),
+                   self_collides=lambda s, d: chain_self_collides(s[0], P.fk, d))
 
 
 def chain_rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
@@ -216,15 +288,17 @@ def chain_rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, s
     """O.collision_costs for the chain: the K x T loop (control.py:81-109 with the chain model).  eps (K, T, n);
     returns S (K,), or with ``details=True`` the dict, dist and clipped (K, T, nd, n) of chain_segment_test.
     ``lo`` / ``hi``: torque limits, a scalar or per joint (the four rules of O.sampled_controls, per joint);
-    ``discs``, ``vel``, ``obstacle_cost``, ``shift``: the collision cost, as O.rollout_costs'."""
+    ``discs``, ``vel``, ``obstacle_cost``, ``shift``: the collision cost, as O.rollout_costs'; ``clearance``,
+    ``self_cost``: the self-collision cost in the same penalty (None: off).  The dict always has flag_self (K, T),
+    e and x (K, T, P) of chain_self_test, mask (K, T) and hits_self (K,), zeros while the self-collision cost is off."""
     return O.collision_costs(chain_model(P), x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
                              expl, k_offset, K_total, gamma, lo, hi, **kw)
 
 
 def step(x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
          P: ChainParams = ChainParams(), **kw):
-    """O.model_step for the chain, with its keywords: gamma, lo, hi, discs, vel, obstacle_cost, hits,
-    visualize_optimal_traj, sampled."""
+    """O.model_step for the chain, with its keywords: gamma, lo, hi, discs, vel, obstacle_cost, hits, clearance,
+    self_cost, self_hits, visualize_optimal_traj, sampled."""
     return O.model_step(chain_model(P), x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
                         expl, **kw)
 

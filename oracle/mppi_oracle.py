@@ -15,7 +15,8 @@ and with workspace obstacles (``discs``: a collision cost inside ``_c`` and
 ``tests/test_obstacle_cpu.py`` to fixtures captured from the reference with
 only those hooks overridden; discs that move (``vel``) by
 ``tests/test_moving_obstacle_cpu.py``.  There is ONE horizon loop
-(``horizon_loop``), ONE collision-cost loop around it (``collision_costs``) and
+(``horizon_loop``), ONE collision-cost loop around it (``collision_costs``: the
+discs and, for the chain, self-collision, in one penalty) and
 ONE update tail (``update_in_place``); the chain (``chain_oracle.py``) runs the
 same three with its own model.
 
@@ -195,9 +196,10 @@ def _controls(u, eps, exploit, lim):
 # start(x0, K) -> state, step(state, v, dt) -> state, cost(state, ref_path, prev_idx, weight) -> (K,),
 # dot(a, v) -> (K,) the control cost a . v in the model's own expression (its bits are pinned),
 # trajectory(x0, controls, dt) -> states, and for the collision cost (collision_costs):
-# collides(state, discs) -> (flag, clear, dist, clipped), the model's collision test, and
-# record(state) -> (ee (K, 2), q (K, n), dq (K, n)), what a state records per step.
-Model = namedtuple("Model", "start step cost dot trajectory collides record")
+# collides(state, discs) -> (flag, clear, dist, clipped), the model's collision test,
+# record(state) -> (ee (K, 2), q (K, n), dq (K, n)), what a state records per step, and
+# self_collides(state, d) -> (flag, e, x, mask), its self-collision test at the clearance d (None: it has none).
+Model = namedtuple("Model", "start step cost dot trajectory collides record self_collides")
 
 
 def arm_model(p: ArmParams = ArmParams()):
@@ -212,7 +214,8 @@ def arm_model(p: ArmParams = ArmParams()):
                  cost=lambda s, ref_path, prev_idx, weight: state_cost(*s, ref_path, prev_idx, weight, p),
                  dot=lambda a, v: a[0] * v[:, 0] + a[1] * v[:, 1],
                  trajectory=lambda x0, controls, dt: rollout_trajectory(x0, controls, dt, p),
-                 collides=lambda s, discs: collides(s[0], s[1], discs, p), record=record)
+                 collides=lambda s, discs: collides(s[0], s[1], discs, p), record=record,
+                 self_collides=None)                       # two links have no non-adjacent pair
 
 
 def horizon_loop(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
@@ -265,32 +268,47 @@ def discs_at(discs, vel, t, dt, shift=0):
 
 def collision_costs(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
                     k_offset=0, K_total=None, gamma=None, lo=None, hi=None, *, discs=None, vel=None,
-                    obstacle_cost=0.0, shift=0, details=False):
+                    obstacle_cost=0.0, shift=0, clearance=None, self_cost=0.0, details=False):
     """S (K,) fp64 of either model's K x T loop (horizon_loop) with the collision cost on ``discs``, which move
-    with ``vel`` (discs_at).
+    with ``vel`` (discs_at), and, with a ``clearance``, the model's self-collision cost in the same penalty.
 
     The collision cost is the reference with ONLY ``_c`` and ``_phi`` (control.py:174-198) overridden to return
     ``... + obstacle_cost * collides(x)``, the penalty added after the x 10000: every step of the horizon whose
     new state collides adds it to its sample's cost and the final state adds it once more (against the centres of
     the last step, so it repeats that step's flag): ``S = S_track + obstacle_cost * hits``, ``hits`` in
-    ``[0, T + 1]``.
+    ``[0, T + 1]``.  With ``clearance`` (not None) the penalty of a state is
+    ``obstacle_cost * flag + self_cost * flag_self``, flag_self from ``model.self_collides(state, clearance)``:
+    ``S = S_track + obstacle_cost * hits + self_cost * hits_self``; a model without one raises ValueError.
 
     ``details=True`` returns a dict instead: S, S_track (K,) (the same loop without the penalty), flag (K, T)
     bool per step's new state, clear (K, T) clearance, hits (K,) = flag.sum(1) + flag[:, -1], dist and clipped
     (K, T) + whatever model.collides returns per state, ee (K, T, 2) end effector, q and dq (K, T, n) joint angles
-    and rates.  Without discs and without details the loop does no collision or bookkeeping work."""
+    and rates; for a model with a self-collision test also flag_self (K, T) bool, e and x (K, T, P) and mask (K, T)
+    of model.self_collides and hits_self (K,), zeros while ``clearance`` is None.  Without discs, clearance and
+    details the loop does no collision or bookkeeping work."""
+    if clearance is not None and model.self_collides is None:
+        raise ValueError("the model has no self-collision test")
     steps, penalty = [], None
-    if discs is not None or details:
+    if discs is not None or clearance is not None or details:
         def penalty(t, state):
-            steps.append(model.collides(state, discs_at(discs, vel, t, dt, shift)) + model.record(state))
-            return obstacle_cost * steps[-1][0]
+            hit = model.collides(state, discs_at(discs, vel, t, dt, shift))
+            own = () if clearance is None else model.self_collides(state, clearance)
+            steps.append(hit + model.record(state) + own)
+            if clearance is None:
+                return obstacle_cost * hit[0]
+            return obstacle_cost * hit[0] + self_cost * own[0]
 
     S, S_track = horizon_loop(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl,
                               k_offset, K_total, gamma, lo, hi, penalty)
     if not details:
         return S
-    rec = {k: np.stack(a, 1) for k, a in zip(("flag", "clear", "dist", "clipped", "ee", "q", "dq"), zip(*steps))}
-    return dict(S=S, S_track=S_track, hits=rec["flag"].sum(1) + rec["flag"][:, -1], **rec)
+    rec = {k: np.stack(a, 1) for k, a in zip(("flag", "clear", "dist", "clipped", "ee", "q", "dq",
+                                              "flag_self", "e", "x", "mask"), zip(*steps))}
+    if clearance is None and model.self_collides is not None:        # the same keys, whatever the keywords
+        off = zip(("flag_self", "e", "x", "mask"), model.self_collides(model.start(x0, eps.shape[0]), 0.0))
+        rec.update({k: np.zeros(a.shape[:1] + eps.shape[1:2] + a.shape[1:], a.dtype) for k, a in off})
+    hits = {h: rec[f].sum(1) + rec[f][:, -1] for h, f in (("hits", "flag"), ("hits_self", "flag_self")) if f in rec}
+    return dict(S=S, S_track=S_track, **hits, **rec)
 
 
 def rollout_costs(x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w,
@@ -473,17 +491,23 @@ def update(S, u_prev, eps, lam, x0, dt, lo=None, hi=None, visualize_optimal_traj
 
 
 def model_step(model, x0, u_prev, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl=0.0,
-               gamma=None, *, lo=None, hi=None, discs=None, vel=None, obstacle_cost=0.0, hits=None,
-               visualize_optimal_traj=True, sampled=False):
-    """One calc_control_input of either model after its waypoint update (control.py:81-152), with limits and
-    (moving) discs when given; ``prev_idx`` is the updated index.  collision_costs(details=True)'s dict joined with
-    update_in_place's.  ``hits`` (K,), when given, replaces the yardstick's own hit counts in S (the device's: a
-    state within rounding of a boundary may fall on either side, and must not move a weight)."""
+               gamma=None, *, lo=None, hi=None, discs=None, vel=None, obstacle_cost=0.0, hits=None, clearance=None,
+               self_cost=0.0, self_hits=None, visualize_optimal_traj=True, sampled=False):
+    """One calc_control_input of either model after its waypoint update (control.py:81-152), with limits,
+    (moving) discs and the self-collision cost when given; ``prev_idx`` is the updated index.
+    collision_costs(details=True)'s dict joined with update_in_place's.  ``hits`` / ``self_hits`` (K,), when either
+    is given, replace the yardstick's own hit counts in S (the device's: a state within rounding of a boundary may
+    fall on either side, and must not move a weight), a None entry the yardstick's own:
+    S = (S_track + obstacle_cost hits) + self_cost hits_self, the second addend only with a ``clearance``."""
     u = np.array(u_prev, dtype=np.float64)
     out = collision_costs(model, x0, u, eps, ref_path, prev_idx, dt, lam, alpha, sigma, stage_w, term_w, expl,
-                          gamma=gamma, lo=lo, hi=hi, discs=discs, vel=vel, obstacle_cost=obstacle_cost, details=True)
-    if hits is not None:
-        out["S"] = out["S_track"] + obstacle_cost * np.asarray(hits, dtype=np.float64)
+                          gamma=gamma, lo=lo, hi=hi, discs=discs, vel=vel, obstacle_cost=obstacle_cost,
+                          clearance=clearance, self_cost=self_cost, details=True)
+    if hits is not None or self_hits is not None:
+        count = lambda given, own: np.asarray(out[own] if given is None else given, dtype=np.float64)  # noqa: E731
+        out["S"] = out["S_track"] + obstacle_cost * count(hits, "hits")
+        if clearance is not None:
+            out["S"] = out["S"] + self_cost * count(self_hits, "hits_self")
     out.update(update_in_place(model, out["S"], u, eps, lam, x0, dt, lo, hi, expl, visualize_optimal_traj, sampled))
     return out
 

@@ -1,13 +1,15 @@
 """What the test files share besides conftest.py's fixtures: the clamp_* / obst_* / asym_* fixture plumbing, run.py's
-constants, the asymmetric arm cases and non-uniform chains, and the GPU tests' helpers (torch and the package are imported inside the functions, so this module
+constants, the asymmetric arm cases and non-uniform chains, the chain tests' uniform chain and Sigma, and the GPU tests' helpers (torch and the package are imported inside the functions, so this module
 imports without either).
 
 The yardsticks themselves live in ``oracle/``: ``mppi_oracle.py`` (the arm, with torque limits and workspace
 obstacles, at rest or moving; the one collision-cost loop and step of either model, ``discs_at``, ``moving_masks``)
-and ``chain_oracle.py`` (the chain, with torque limits and the same obstacles through ``chain_collides``;
-``chain_segment_test``, ``chain_touch_mask``, ``chain_moving_masks``), pinned to these fixtures by
+and ``chain_oracle.py`` (the chain, with torque limits, the same obstacles through ``chain_collides`` and
+self-collision through ``chain_self_collides``; ``chain_segment_test``, ``chain_touch_mask``, ``chain_moving_masks``,
+``chain_self_test``), pinned to these fixtures by
 test_oracle_golden.py, test_clamp_cpu.py, test_chain_clamp_cpu.py, test_obstacle_cpu.py, test_chain_obstacle_cpu.py,
-test_moving_obstacle_cpu.py, test_chain_moving_obstacle_cpu.py and test_chain_oracle.py.
+test_moving_obstacle_cpu.py, test_chain_moving_obstacle_cpu.py and test_chain_oracle.py (the self-collision predicate
+by test_chain_self_collision_cpu.py).
 """
 import glob
 import os
@@ -91,6 +93,21 @@ def _engine(K, T, lps=0, K_total=None, k_offset=0, u_min=None, u_max=None, clamp
                          kw["stage_cost_weight"], kw["terminal_cost_weight"], kw["param_exploration"],
                          ArmParams(), K_total=K_total, k_offset=k_offset, device=0, lanes_per_sample=lps,
                          u_min=u_min, u_max=u_max, clamp_nominal=clamp_nominal)
+
+
+def _chains(n):
+    """n uniform slender links of 1 kg and 2 m total reach (config 5's arm at n = 7): the engine's and the oracle's."""
+    import chain_oracle as CO
+    import mppi_robotarm_amd.chain as chain_mod
+    L = 2.0 / n
+    kw = dict(m=(1.0,) * n, l=(L,) * n, lc=(L / 2,) * n, I=(L * L / 12.0,) * n, fk=(L,) * n, J=(0.1,) * n, b=(1.0,) * n)
+    return chain_mod.ChainParams(**kw), CO.ChainParams(**kw)
+
+
+def _sigma(n):
+    """The chain tests' Sigma: config 5's at n = 7, a diagonal ramp otherwise."""
+    from mppi_robotarm_amd.chain import CHAIN7_SIGMA
+    return CHAIN7_SIGMA.copy() if n == 7 else np.diag(np.linspace(8.0, 1.0, n))
 
 
 def _ctrl(g, paths, **kw):

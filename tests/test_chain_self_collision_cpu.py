@@ -1,10 +1,11 @@
 """CPU: the self-collision cost of the n-link chain (a cost on non-adjacent link pairs).
 
-  * tests/selfcol.py's fp64 predicate, the yardstick of the GPU tests, against a brute-force segment distance (each
-    segment sampled at 2001 points; agreement to the sampling step) on random poses and on hand-made crossing,
-    touching-at-an-end and parallel-overlapping pairs;
+  * oracle/chain_oracle.py's fp64 predicate (chain_self_test), the yardstick of the GPU tests, against a brute-force
+    segment distance (each segment sampled at 2001 points; agreement to the sampling step) on random poses and on
+    hand-made crossing, touching-at-an-end and parallel-overlapping pairs;
   * the pair enumeration at n = 3, 4, 7 (1, 3 and 15 pairs) and the empty mask at n = 2;
-  * its penalty loop with the self cost 0 is oracle/chain_oracle.py's rollout cost, bit for bit, with and without discs;
+  * the oracle's rollout cost with a clearance and the self cost 0 is its rollout cost without a clearance, bit for bit,
+    with and without discs;
   * the C ABI: both entry points declared in the header and bound by _native;
   * ChainEngine.check_self_collision and the drop-in's by-value key.
 """
@@ -15,7 +16,6 @@ import numpy as np
 import pytest
 
 import chain_oracle as CO
-import selfcol as SC
 from conftest import ROOT
 from mppi_robotarm_amd import _native as N
 from mppi_robotarm_amd.chain import ChainEngine, ChainMPPIController, ChainParams
@@ -32,8 +32,16 @@ def _uniform(n, reach=2.0):
 
 def _segments(q, fk):
     th = np.cumsum(q)
-    jx, jy = SC.joints(np.cos(th), np.sin(th), fk)
+    jx, jy = CO.chain_joints(np.cos(th), np.sin(th), fk)
     return [((jx[a], jy[a]), (jx[a + 1], jy[a + 1])) for a in range(len(q))]
+
+
+def _brute_distance(p0, p1, q0, q1, m=2001):
+    """The distance of two segments by sampling each at m points (an upper bound, within the sampling step)."""
+    t = np.linspace(0.0, 1.0, m)[:, None]
+    A = (1.0 - t) * np.asarray(p0, dtype=np.float64) + t * np.asarray(p1, dtype=np.float64)
+    B = (1.0 - t) * np.asarray(q0, dtype=np.float64) + t * np.asarray(q1, dtype=np.float64)
+    return float(np.sqrt(np.min((A[:, None, 0] - B[None, :, 0]) ** 2 + (A[:, None, 1] - B[None, :, 1]) ** 2)))
 
 
 def _brute_cross(p0, p1, q0, q1):
@@ -58,10 +66,10 @@ def test_predicate_against_brute_force_on_random_poses(n):
         bend = rng.normal(0.0, 1.6, n - 1) if it % 2 else rng.uniform(1.2, 2.9, n - 1)
         q = np.concatenate([[rng.uniform(-np.pi, np.pi)], bend])
         th = np.cumsum(q)
-        e, x, _ = SC.self_test(np.cos(th), np.sin(th), fk)
+        e, x, _ = CO.chain_self_test(np.cos(th), np.sin(th), fk)
         seg = _segments(q, fk)
-        for i, (a, b) in enumerate(SC.pairs(n)):
-            brute = SC.brute_distance(*seg[a], *seg[b], m=M)
+        for i, (a, b) in enumerate(CO.chain_self_pairs(n)):
+            brute = _brute_distance(*seg[a], *seg[b], m=M)
             step = max(fk[a], fk[b]) / (M - 1)
             want_x = _brute_cross(*seg[a], *seg[b])
             assert bool(x[i]) == want_x, (q, a, b)
@@ -80,50 +88,50 @@ def test_hand_made_pairs():
     # link 2 comes back across link 0: up 1, right 0.5, then down-left through the first link
     q = np.array([pi / 2, -pi / 2, -3 * pi / 4])
     th = np.cumsum(q)
-    e, x, m = SC.self_test(np.cos(th), np.sin(th), fk, 0.0)
+    e, x, m = CO.chain_self_test(np.cos(th), np.sin(th), fk, 0.0)
     assert x[0] and m == 1
-    assert SC.brute_distance(*_segments(q, fk)[0], *_segments(q, fk)[2]) < 1e-3
+    assert _brute_distance(*_segments(q, fk)[0], *_segments(q, fk)[2]) < 1e-3
     # touching at an end (exact direction values, so nothing is left to rounding): link 2 comes straight back down
     # link 1 and ends on the far end of link 0; an end on the other's line is on neither side: not a proper crossing
     fk = np.array([4.0, 3.0, 3.0])
     c, s = np.array([1.0, 0.0, 0.0]), np.array([0.0, 1.0, -1.0])
-    e, x, m0 = SC.self_test(c, s, fk, 0.0)
+    e, x, m0 = CO.chain_self_test(c, s, fk, 0.0)
     assert e[0] == 0.0 and not x[0] and m0 == 0        # d = 0 counts crossings only
-    assert SC.self_test(c, s, fk, 1e-9)[2] == 1        # any clearance catches the touch
+    assert CO.chain_self_test(c, s, fk, 1e-9)[2] == 1        # any clearance catches the touch
     # ... and ends in the interior of link 0 when link 1 leans back over it (a 3-4-5 triangle)
     fk = np.array([4.0, 5.0, 4.0])
     c, s = np.array([1.0, -0.6, 0.0]), np.array([0.0, 0.8, -1.0])
-    e, x, m0 = SC.self_test(c, s, fk, 0.0)
+    e, x, m0 = CO.chain_self_test(c, s, fk, 0.0)
     assert e[0] == 0.0 and not x[0] and m0 == 0
-    e, x, m0 = SC.self_test(c, s, fk + np.array([0.0, 0.0, 0.5]), 0.0)
+    e, x, m0 = CO.chain_self_test(c, s, fk + np.array([0.0, 0.0, 0.5]), 0.0)
     assert x[0] and m0 == 1                            # half a metre longer, it goes through
     # parallel, overlapping: link 2 runs back beside link 0 at distance 0.25
     fk = np.array([1.0, 0.25, 0.8])
     c, s = np.array([1.0, 0.0, -1.0]), np.array([0.0, 1.0, 0.0])
-    e, x, m = SC.self_test(c, s, fk, 0.25)
+    e, x, m = CO.chain_self_test(c, s, fk, 0.25)
     assert e[0] == 0.25 and not x[0] and m == 0        # e < d is strict
-    assert SC.self_test(c, s, fk, 0.2500001)[2] == 1
-    jx, jy = SC.joints(c, s, fk)
-    assert abs(SC.brute_distance((jx[0], jy[0]), (jx[1], jy[1]), (jx[2], jy[2]), (jx[3], jy[3])) - 0.25) < 1e-3
+    assert CO.chain_self_test(c, s, fk, 0.2500001)[2] == 1
+    jx, jy = CO.chain_joints(c, s, fk)
+    assert abs(_brute_distance((jx[0], jy[0]), (jx[1], jy[1]), (jx[2], jy[2]), (jx[3], jy[3])) - 0.25) < 1e-3
 
 
 def test_pair_enumeration():
-    assert SC.pairs(3) == [(0, 2)]
-    assert SC.pairs(4) == [(0, 2), (0, 3), (1, 3)]
-    p7 = SC.pairs(7)
+    assert CO.chain_self_pairs(3) == [(0, 2)]
+    assert CO.chain_self_pairs(4) == [(0, 2), (0, 3), (1, 3)]
+    p7 = CO.chain_self_pairs(7)
     assert len(p7) == 15 and p7[:5] == [(0, 2), (0, 3), (0, 4), (0, 5), (0, 6)] and p7[5] == (1, 3) and p7[-1] == (4, 6)
-    assert SC.pairs(2) == []
+    assert CO.chain_self_pairs(2) == []
     # a tight coil sets every bit, and only the 15
     q = np.array([0.3] + [2.0 * np.pi / 3.0 * 0.99] * 6)
     th = np.cumsum(q)
-    _, _, m = SC.self_test(np.cos(th), np.sin(th), [2.0 / 7.0] * 7, 0.5)
+    _, _, m = CO.chain_self_test(np.cos(th), np.sin(th), [2.0 / 7.0] * 7, 0.5)
     assert m == (1 << 15) - 1
 
 
 def test_two_links_have_no_pair():
     rng = np.random.default_rng(0)
     th = rng.uniform(-3, 3, (50, 2))
-    e, x, m = SC.self_test(np.cos(th), np.sin(th), [1.0, 1.0], 10.0)
+    e, x, m = CO.chain_self_test(np.cos(th), np.sin(th), [1.0, 1.0], 10.0)
     assert e.shape == (50, 0) and x.shape == (50, 0) and not m.any() and m.dtype == np.uint32
 
 
@@ -140,19 +148,21 @@ def test_penalty_loop_with_zero_self_cost_is_the_oracles_rollout(with_discs, pat
     discs = np.array([[0.3, 0.5, 0.2], [-0.2, 0.6, 0.1]]) if with_discs else None
     args = (x0, u, eps, paths["xydq_circle"], 40, 0.03, 100.0, 0.98, sigma, [0.5, 0.5, 5.0, 5.0], [5.0, 5.0, 50.0, 50.0])
     want = CO.chain_rollout_costs(*args, 0.0, P, discs=discs, obstacle_cost=1.0e4, details=True)
-    got = SC.rollout_costs(P, *args, discs=discs, obstacle_cost=1.0e4, clearance=0.05, self_cost=0.0)
+    got = CO.chain_rollout_costs(*args, 0.0, P, discs=discs, obstacle_cost=1.0e4, clearance=0.05, self_cost=0.0,
+                                 details=True)
     assert np.array_equal(got["S"], want["S"]) and np.array_equal(got["S_track"], want["S_track"])
-    assert np.array_equal(got["hits_disc"], want["hits"])
+    assert np.array_equal(got["hits"], want["hits"])
     if with_discs:
         assert want["hits"].any()
     # and with a cost: S_track untouched, S = S_track + both penalties to rounding, the counts from the flags
-    r = SC.rollout_costs(P, *args, discs=discs, obstacle_cost=1.0e4, clearance=0.3, self_cost=7.0)
+    r = CO.chain_rollout_costs(*args, 0.0, P, discs=discs, obstacle_cost=1.0e4, clearance=0.3, self_cost=7.0,
+                               details=True)
     assert np.array_equal(r["S_track"], want["S_track"])
     assert np.array_equal(r["hits_self"], r["flag_self"].sum(1) + r["flag_self"][:, -1])
     assert r["hits_self"].any() and r["hits_self"].max() <= T + 1
-    np.testing.assert_allclose(r["S"], r["S_track"] + 1.0e4 * r["hits_disc"] + 7.0 * r["hits_self"], rtol=1e-13)
-    sub = SC.rollout_costs(P, *args, discs=discs, obstacle_cost=1.0e4, clearance=0.3, self_cost=7.0,
-                           hits=(None, np.zeros(K, dtype=int)))
+    np.testing.assert_allclose(r["S"], r["S_track"] + 1.0e4 * r["hits"] + 7.0 * r["hits_self"], rtol=1e-13)
+    sub = CO.step(*args, 0.0, P, discs=discs, obstacle_cost=1.0e4, clearance=0.3, self_cost=7.0,
+                  self_hits=np.zeros(K, dtype=int))
     np.testing.assert_allclose(sub["S"], want["S"], rtol=1e-15)
 
 

@@ -18,7 +18,7 @@ import torch
 
 import merge_steer as M
 from conftest import record
-from helpers import _gpu  # noqa: F401
+from helpers import _chains, _gpu, _sigma  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,32 +28,21 @@ W, TW = [0.5, 0.5, 5.0, 5.0], [5.0, 5.0, 50.0, 50.0]
 _POOLS = {}
 
 
-def _sigma(n):
-    from mppi_robotarm_amd.chain import CHAIN7_SIGMA
-    return CHAIN7_SIGMA.copy() if n == 7 else np.diag(np.linspace(8.0, 1.0, n))
-
-
 def _engine(n, K, T, precision, lps):
-    """n uniform slender links of 1 kg and 2 m total reach (config 5's arm at n = 7)."""
-    from mppi_robotarm_amd.chain import ChainEngine, ChainParams
-    L = 2.0 / n
-    P = ChainParams(m=(1.0,) * n, l=(L,) * n, lc=(L / 2,) * n, I=(L * L / 12.0,) * n, fk=(L,) * n, J=(0.1,) * n,
-                    b=(1.0,) * n)
-    eng = ChainEngine(K, T, 0.006, LAM, 0.98, _sigma(n), W, TW, 0.0, P, device=0, precision=precision,
+    """The uniform chain of helpers._chains (config 5's arm at n = 7)."""
+    from mppi_robotarm_amd.chain import ChainEngine
+    eng = ChainEngine(K, T, 0.006, LAM, 0.98, _sigma(n), W, TW, 0.0, _chains(n)[0], device=0, precision=precision,
                       lanes_per_sample=lps)
     assert eng.lanes_per_sample == lps and eng.threads == 256
     return eng
 
 
 def _inputs(eng, paths):
-    from mppi_robotarm_amd.chain import gravity_torque, ChainParams
+    from mppi_robotarm_amd.chain import gravity_torque
     n = eng.n
-    L = 2.0 / n
     q = np.array([1.4] + [-2.2 / (n - 1)] * (n - 1))
-    P = ChainParams(m=(1.0,) * n, l=(L,) * n, lc=(L / 2,) * n, I=(L * L / 12.0,) * n, fk=(L,) * n, J=(0.1,) * n,
-                    b=(1.0,) * n)
     eng.set_step_inputs(np.concatenate([q, np.zeros(n)]), paths["xydq_circle"][40:70],
-                        np.tile(gravity_torque(q, P), (eng.T, 1)))
+                        np.tile(gravity_torque(q, _chains(n)[0]), (eng.T, 1)))
 
 
 def _rollout(eng, cols, paths, partial=False):

@@ -21,9 +21,9 @@ pytestmark = pytest.mark.gpu
 import chain_oracle as CO  # noqa: E402
 import mppi_oracle as O  # noqa: E402
 from conftest import GOLDEN  # noqa: E402
-from helpers import _gpu, _urel, asym_chain_inputs  # noqa: E402, F401
+from helpers import _chains, _gpu, _sigma, _urel, asym_chain_inputs  # noqa: E402, F401
 from test_gpu_chain_obstacles import (ALPHA, COSTS, DT, FORM_IDS, FORMS, NS, S_TOL, TW, U_TOL, W, T,  # noqa: E402
-                                      _bits, _chains, _engine, _hits_from_masks, _problem, _S, _sigma, _stage, edge,
+                                      _bits, _engine, _hits_from_masks, _problem, _S, _stage, edge,
                                       place_discs)
 
 PAIR_CAP = 0.005            # at most 0.5 % of the (sample, step, link, disc) pairs may differ, all within EDGE

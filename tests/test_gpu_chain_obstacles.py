@@ -35,7 +35,7 @@ pytestmark = pytest.mark.gpu
 import chain_oracle as CO  # noqa: E402
 import mppi_oracle as O  # noqa: E402
 from chain_oracle import chain_collides, chain_segment_test, chain_touch_mask  # noqa: E402
-from helpers import OBST_STEPS, _gpu, _inside, _urel, load_obst_step  # noqa: E402, F401
+from helpers import OBST_STEPS, _chains, _gpu, _inside, _sigma, _urel, load_obst_step  # noqa: E402, F401
 
 U_TOL = 1e-4
 S_TOL = 5e-5
@@ -49,19 +49,6 @@ NS = [2, 3, 7]
 FORMS = [("f32", 1, 300), ("f32", 4, 100), ("f64", 1, 300)]
 FORM_IDS = ["f32-lps1", "f32-lps4", "f64"]
 COSTS = ((8, 1.0e10), (3, 3.0e6), (1, 7.0))   # (discs, cost): integer-valued costs, w * hits is exact
-
-
-def _chains(n):
-    """n uniform slender links of 1 kg and 2 m total reach (config 5's arm at n = 7): the engine's and the oracle's."""
-    import mppi_robotarm_amd.chain as chain_mod
-    L = REACH / n
-    kw = dict(m=(1.0,) * n, l=(L,) * n, lc=(L / 2,) * n, I=(L * L / 12.0,) * n, fk=(L,) * n, J=(0.1,) * n, b=(1.0,) * n)
-    return chain_mod.ChainParams(**kw), CO.ChainParams(**kw)
-
-
-def _sigma(n):
-    from mppi_robotarm_amd.chain import CHAIN7_SIGMA
-    return CHAIN7_SIGMA.copy() if n == 7 else np.diag(np.linspace(8.0, 1.0, n))
 
 
 def edge(n, discs):

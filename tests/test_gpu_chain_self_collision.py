@@ -1,8 +1,8 @@
 """GPU: the self-collision cost of the n-link chain (mppi_chain_set_self_collision; the SELF instantiations of
 chain_rollout_kernel in its three forms: fp32 with one lane per sample, fp32 with a quad per sample, fp64).
 
-Yardstick: tests/selfcol.py, the fp64 predicate and its penalty on oracle/chain_oracle.py's model through
-O.horizon_loop's hook (pinned by test_chain_self_collision_cpu.py).  Modelled on test_gpu_chain_obstacles.py, whose
+Yardstick: oracle/chain_oracle.py, the fp64 predicate (chain_self_test) and its penalty beside the discs' in
+O.collision_costs (pinned by test_chain_self_collision_cpu.py).  Modelled on test_gpu_chain_obstacles.py, whose
 constants and helpers it uses: S 5e-5, weights 1e-10, nominal 1e-4, hit-count agreement >= 0.99, EDGE_CAP 0.05.
 
 Shapes, the smallest at which each form can go wrong: n in {3, 4, 7} (one pair, with the quad's pad link; an even chain;
@@ -42,11 +42,10 @@ pytestmark = pytest.mark.gpu
 
 import chain_oracle as CO  # noqa: E402
 import mppi_oracle as O  # noqa: E402
-import selfcol as SC  # noqa: E402
 from conftest import STEP_FIXTURES, load_step  # noqa: E402
-from helpers import _inside, _urel  # noqa: E402
+from helpers import _chains, _inside, _sigma, _urel  # noqa: E402
 from test_gpu_chain_obstacles import (ALPHA, DT, EDGE_CAP, FORM_IDS, FORMS, REACH, S_TOL, TW, U_TOL, W, W_TOL, T,  # noqa: E402
-                                      _chains, _engine, _hits_from_masks, _S, _sigma, place_discs)
+                                      _engine, _hits_from_masks, _S, place_discs)
 
 NS = [3, 4, 7]
 OPEN = {3: 2.08, 4: 1.55, 7: 0.86}
@@ -71,11 +70,11 @@ _prob = {}
 
 
 def _args(p, n, paths, lam):
-    return (_chains(n)[1], p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW)
+    return (p["x0"], p["u"], p["eps"], paths["xydq_circle"], 40, DT, lam, ALPHA, _sigma(n), W, TW, 0.0, _chains(n)[1])
 
 
 def _ref(p, n, paths, lam=100.0, **kw):
-    return SC.rollout_costs(*_args(p, n, paths, lam), **kw)
+    return CO.chain_rollout_costs(*_args(p, n, paths, lam), details=True, **kw)
 
 
 def _near_edge(e, x, d, E):
@@ -110,7 +109,7 @@ def _coils_fail(ps, n):
     crosses in some state, and at most EDGE_CAP of the entries lie within EDGE of a boundary."""
     e = np.concatenate([p["free"]["e"] for _, p in ps], 1)                 # (K, poses * T, P)
     x = np.concatenate([p["free"]["x"] for _, p in ps], 1)
-    for i, pair in enumerate(SC.pairs(n)):
+    for i, pair in enumerate(CO.chain_self_pairs(n)):
         bits = np.concatenate([(x[..., i] | (e[..., i] < d)).ravel() for d in COIL_D])
         if not bits.any() or bits.all():
             return f"the bit of pair {pair} is {'always' if bits.all() else 'never'} set"
@@ -155,7 +154,7 @@ def _weights_fail(p, n, paths):
         return f"with torque limits {share:.0%} of the samples self-collide"
     cases = [(lam, w, d, None, None) for lam, w in LAM_COST for d in (d0, d0 + D_STEP)] + [(100.0, 1.0e10, dc, lo, hi)]
     for lam, w, d, a, b in cases:
-        r = SC.step(*_args(p, n, paths, lam), lo=a, hi=b, clearance=d, self_cost=w)
+        r = CO.step(*_args(p, n, paths, lam), lo=a, hi=b, clearance=d, self_cost=w)
         for _ in range(4):
             Sp = r["S"] * (1.0 + 2.0 ** -20 * rng.uniform(-1.0, 1.0, r["S"].shape))
             moved = _urel(O.weighted_noise(O.compute_weights(Sp, lam), p["eps"]), r["w_eps_raw"])
@@ -219,7 +218,7 @@ def _disc_hits(eng, noise):
 def test_mask_parity_on_the_devices_own_directions(precision, lps, K, n, paths):
     fk = _chains(n)[1].fk
     E = edge(n)
-    P = len(SC.pairs(n))
+    P = len(CO.chain_self_pairs(n))
     bit = np.uint32(1) << np.arange(P, dtype=np.uint32)
     eng = _engine(n, K, precision=precision, lps=lps)
     seen_set, seen_clear = np.zeros(P, bool), np.zeros(P, bool)
@@ -231,7 +230,7 @@ def test_mask_parity_on_the_devices_own_directions(precision, lps, K, n, paths):
             mask, dirs = eng.self_hits(noise)
             assert mask.shape == (K, T) and mask.dtype == np.uint32 and dirs.shape == (K, T, 2 * n)
             assert float(np.max(np.abs(dirs - np.concatenate([np.cos(th), np.sin(th)], -1)))) < 1e-4
-            e, x, want = SC.self_test(dirs[..., :n], dirs[..., n:], fk, d)
+            e, x, want = CO.chain_self_test(dirs[..., :n], dirs[..., n:], fk, d)
             differ = ((mask[..., None] ^ want[..., None]) & bit) != 0             # (K, T, P)
             near = _near_edge(e, x, d, E)
             worst = float(np.minimum(np.abs(e - d), e)[differ].max()) if differ.any() else 0.0
@@ -328,7 +327,7 @@ def test_weighted_noise_and_nominal(precision, lps, K, n, lam, w, paths):
         S, weps = _S(eng, noise), eng.weighted_noise()
         hs = _self_hits(eng, noise)
         seen.append(hs)
-        r = SC.step(*_args(p, n, paths, lam), clearance=d, self_cost=w, hits=(None, hs))
+        r = CO.step(*_args(p, n, paths, lam), clearance=d, self_cost=w, self_hits=hs)
         assert float(np.mean(hs == r["hits_self"])) >= 0.99
         host = O.weighted_noise(O.compute_weights(S, lam), p["eps"])
         srel = float(np.max(np.abs(S - r["S"]) / np.abs(r["S"])))
@@ -368,7 +367,7 @@ def test_decomposition_with_torque_limits(precision, lps, K, n, paths):
     hs = _self_hits(eng, noise)
     assert hs.any() and not np.all(hs > 0)
     assert np.array_equal(S, S_free + w * hs.astype(np.float64))
-    r = SC.step(*_args(p, n, paths, 100.0), lo=lo, hi=hi, clearance=d, self_cost=w, hits=(None, hs))
+    r = CO.step(*_args(p, n, paths, 100.0), lo=lo, hi=hi, clearance=d, self_cost=w, self_hits=hs)
     assert float(np.mean(hs == r["hits_self"])) >= 0.99
     eng.rollout(noise, fused_update=True)
     u = eng.nominal()
@@ -394,8 +393,8 @@ def _moving_disc(n, K, paths):
                 ang = 0.4 + k * np.pi / 4
                 v = (d0[2] / (T * DT)) * np.array([[np.cos(ang), np.sin(ang)]])
                 disc = np.array([[d0[0] - v[0, 0] * T * DT, d0[1] - v[0, 1] * T * DT, d0[2]]])
-                move = _ref(p, n, paths, discs=disc, vel=v, obstacle_cost=1.0)["hits_disc"]
-                rest = _ref(p, n, paths, discs=disc, obstacle_cost=1.0)["hits_disc"]
+                move = _ref(p, n, paths, discs=disc, vel=v, obstacle_cost=1.0)["hits"]
+                rest = _ref(p, n, paths, discs=disc, obstacle_cost=1.0)["hits"]
                 if float(np.mean(move != rest)) >= 0.10 and 0.10 <= float(np.mean(move > 0)) <= 0.90:
                     _moving[(n, K)] = (disc, v)
                     break
@@ -423,7 +422,7 @@ def test_decomposition_with_a_moving_disc(precision, lps, K, n, paths):
     assert hd.any() and hs.any()
     assert np.array_equal(S, (S_free + DISC_COST * hd.astype(np.float64)) + w * hs.astype(np.float64))
     r = _ref(p, n, paths, 3.0e6, discs=disc, vel=v, obstacle_cost=DISC_COST, clearance=p["d"], self_cost=w)
-    assert float(np.mean(hd == r["hits_disc"])) >= 0.99 and float(np.mean(hs == r["hits_self"])) >= 0.99
+    assert float(np.mean(hd == r["hits"])) >= 0.99 and float(np.mean(hs == r["hits_self"])) >= 0.99
     eng.close()
 
 
@@ -545,7 +544,7 @@ def test_dropin_keeps_the_arm_off_itself(precision, paths):
     path = paths["xydq_circle"]
     q0 = np.array([1.4] + [OPEN[n]] * (n - 1))
     x = np.concatenate([q0, np.zeros(n)])
-    _, e0, x0c, _ = SC.self_collides(q0, Po.fk, 0.0)
+    _, e0, x0c, _ = CO.chain_self_collides(q0, Po.fk, 0.0)
     dt, T_, K_ = 0.006, 16, 2048
     # over 16 steps of 6 ms the closest pair (9 cm apart at the start) moves by millimetres: the clearance is taken from
     # the yardstick's own rollouts under the controller's Sigma, the 5th percentile of their closest approach rounded
@@ -553,7 +552,8 @@ def test_dropin_keeps_the_arm_off_itself(precision, paths):
     rng = np.random.default_rng(11)
     eps = rng.normal(size=(256, T_, n)) * np.sqrt(np.diag(CHAIN7_SIGMA))
     ug = gravity_torque(q0, P)
-    ref = SC.rollout_costs(Po, x, np.tile(ug, (T_, 1)), eps, path, 0, dt, 100.0, 0.98, CHAIN7_SIGMA, W, TW, clearance=0.0)
+    ref = CO.chain_rollout_costs(x, np.tile(ug, (T_, 1)), eps, path, 0, dt, 100.0, 0.98, CHAIN7_SIGMA, W, TW, 0.0, Po,
+                                 clearance=0.0, details=True)
     d = round(float(np.quantile(ref["e"].min((1, 2)), 0.05)), 4)
     assert 0.03 < d < float(e0.min()) - 1e-3 and not x0c.any() and not ref["x"].any()
     assert 0.01 <= float(np.mean(ref["e"].min((1, 2)) < d)) <= 0.50
@@ -576,7 +576,7 @@ def test_dropin_keeps_the_arm_off_itself(precision, paths):
         paid += int(np.sum(c.last_S >= 1.0e10))
         qn, dqn = CO.chain_forward_dynamics(x[None, :n], x[None, n:], u0[None, :], dt, Po)
         x = np.concatenate([qn[0], dqn[0]])
-        assert not SC.self_collides(x[:n], Po.fk, d)[0]
+        assert not CO.chain_self_collides(x[:n], Po.fk, d)[0]
     assert paid > 0                                           # the cost was in reach of the sampled rollouts
     # an in-place change: a clearance wider than the reach, every sample pays at every step
     c.self_clearance = 10.0
