@@ -1,6 +1,7 @@
 """What the test files share besides conftest.py's fixtures: the clamp_* / obst_* / asym_* fixture plumbing, run.py's
-constants, the asymmetric arm cases and non-uniform chains, the chain tests' uniform chain and Sigma, and the GPU tests' helpers (torch and the package are imported inside the functions, so this module
-imports without either).
+constants, the asymmetric arm cases and non-uniform chains, the chain tests' uniform chain and Sigma, the cases of the
+chain's fused update (UPDATE_*: test_gpu_chain_update.py and test_chain_update_cpu.py) and the GPU tests' helpers (torch
+and the package are imported inside the functions, so this module imports without either).
 
 The yardsticks themselves live in ``oracle/``: ``mppi_oracle.py`` (the arm, with torque limits and workspace
 obstacles, at rest or moving; the one collision-cost loop and step of either model, ``discs_at``, ``moving_masks``)
@@ -242,3 +243,124 @@ def asym_obstacle_problem(g, cfg, x0, prev, u, eps, paths):
     c2 = a * unit(te) + side * 0.8 * r2 * normal(te)
     discs = np.array([[c0[0], c0[1], r0], [c1[0], c1[1], 0.015], [c2[0], c2[1], r2], [-0.05, -0.02, 0.05]])
     return dict(free=free, discs=discs)
+
+
+# ---------------------------------------------------------------- the chain's fused update (chain_update_block)
+# test_gpu_chain_update.py runs it on the device, test_chain_update_cpu.py proves on the CPU what its cases rely on.
+
+UPDATE_NS = (2, 3, 4, 5, 6, 7)
+# 5: the device minimum; below 10 every window reflects at both ends; 6, 7, 11, 13, 125, 127: T % 4 in {1, 2, 3}, a
+# tail thread whose last windows lie past T; 127, 128: the full thread map and the tid % MPPI_MAX_T row split
+UPDATE_TS = (5, 6, 7, 9, 11, 13, 125, 127, 128)
+# (precision, lanes per sample, K): test_gpu_chain_obstacles.FORMS, two workgroups with a ragged second one in each
+UPDATE_FORMS = [("f32", 1, 300), ("f32", 4, 100), ("f64", 1, 300)]
+UPDATE_FORM_IDS = ["f32-lps1", "f32-lps4", "f64"]
+UPDATE_WIN = slice(40, 70)
+UPDATE_DT, UPDATE_ALPHA = 0.006, 0.98
+UPDATE_W, UPDATE_TW = [0.5, 0.5, 5.0, 5.0], [5.0, 5.0, 50.0, 50.0]
+# lambda per n: the smallest power of ten at which the control-cost share of every single joint,
+# sum_t a_t[d] v[k, t, d], is a median >= 3e-4 of S over the samples at T = 6 and T = 128 of asym_chain_inputs (the
+# last joint carries the least torque and sets it: 2.6e-4 .. 1.1e-3 at these values, a decade less one power below),
+# so that a wrong a_t row of any joint moves S by 100 x the fp32 bound of 1e-6 with room to spare
+# (test_chain_update_cpu.py asserts the 1e-4).  gamma = lambda (1 - alpha) scales a_t.
+UPDATE_LAMBDA = {2: 1.0e3, 3: 1.0e5, 4: 1.0e4, 5: 1.0e4, 6: 1.0e5, 7: 1.0e4}
+UPDATE_S_RTOL = {"f32": 1e-6, "f64": 1e-12}   # test_chain_fused_update_matches_host_update's bounds on S
+
+
+def update_seed(n):
+    """The Philox seed of the update tests' draws at n links."""
+    return 40 + n
+
+
+def shift_nominal(un):
+    """control.py:148-149: the rows moved up by one, the last one kept."""
+    return np.concatenate([un[1:], un[-1:]], 0)
+
+
+def median10(w):
+    """control.py:319-327: scipy's median of 10 with reflected ends, per column."""
+    from scipy.ndimage import median_filter
+    return np.stack([median_filter(w[:, d], size=10, mode="reflect") for d in range(w.shape[1])], 1)
+
+
+def reflected_windows(T):
+    """(T, 10) indices of the windows t - 5 .. t + 4 reflected into [0, T) ('reflect': -1 -> 0, T -> T - 1), T >= 5."""
+    m = np.arange(T)[:, None] + np.arange(-5, 5)[None]
+    m = np.mod(m, 2 * T)
+    return np.where(m >= T, 2 * T - 1 - m, m)
+
+
+def sorted_median10(w):
+    """The same filter without SciPy: rank 5 of np.sort over the reflected index list."""
+    return np.sort(w[reflected_windows(w.shape[0])], axis=1)[:, 5]
+
+
+def expected_nominal(u, w, lo=None, hi=None):
+    """The fused update's nominal from the launch's own weighted noise w: shift(clip(u + median10(w)))."""
+    un = u + median10(w)
+    return shift_nominal(un if lo is None else np.clip(un, lo, hi))
+
+
+def update_reference(n, T, paths, K=300, lo=None, hi=None, lam=None):
+    """The fp64 oracle's update before its shift and clip, u + median10(w_eps), of asym_chain_inputs(n, T) at
+    `lam` (None: UPDATE_LAMBDA[n]) on the host restatement of the device's Philox draw (philox_ref.chain_noise: the
+    device's values to ~1e-6), with the sampled controls clipped to lo / hi when given.  Returns (un (T, n), S (K,),
+    u, eps)."""
+    import chain_oracle as CO
+    import philox_ref
+    Po, x0, sig, u = asym_chain_inputs(n, T, CO)
+    lam = UPDATE_LAMBDA[n] if lam is None else lam
+    eps = philox_ref.chain_noise(K, T, n, 0, update_seed(n), 0, sig).transpose(2, 0, 1)
+    eps = eps.astype(np.float32).astype(np.float64)
+    S = CO.chain_rollout_costs(x0, u, eps, paths["xydq_circle"], UPDATE_WIN.start, UPDATE_DT, lam, UPDATE_ALPHA, sig,
+                               UPDATE_W, UPDATE_TW, 0.0, Po, lo=lo, hi=hi)
+    wk = np.exp(-(S - S.min()) / lam)
+    w = np.einsum("k,ktd->td", wk / wk.sum(), eps)
+    return u + median10(w), S, u, eps
+
+
+_UPDATE_LIMITS = {}
+
+
+UPDATE_CLAMP_LAMBDA = 1.0e3   # the torque-limit cases' lambda, the same at every n
+
+
+def update_limits(n, T, paths):
+    """Torque limits inside the spread of the updated nominal, distinct per joint and per side: quantiles of the
+    columns of update_reference's unlimited u + filt at UPDATE_CLAMP_LAMBDA, from (0.05, 0.95) at joint 0 to
+    (0.15, 0.85) at the last.  The limits change the weights (mode 2 clips the sampled controls too), and at T = 9
+    every window holds nearly the same values, so a column of the filtered noise moves as a whole: the share that
+    the limits clip in the run that has them lies between 0.18 and 0.84 over the cases of test_chain_update_cpu.py,
+    which asserts (0.1, 0.9).  Computed once per (n, T) and left unchanged."""
+    if (n, T) not in _UPDATE_LIMITS:
+        un = update_reference(n, T, paths, lam=UPDATE_CLAMP_LAMBDA)[0]
+        lo = np.array([np.quantile(un[:, d], q) for d, q in enumerate(np.linspace(0.05, 0.15, n))])
+        hi = np.array([np.quantile(un[:, d], q) for d, q in enumerate(np.linspace(0.95, 0.85, n))])
+        lo.setflags(write=False)
+        hi.setflags(write=False)
+        _UPDATE_LIMITS[(n, T)] = (lo, hi)
+    return _UPDATE_LIMITS[(n, T)]
+
+
+def sparse_steps(T):
+    """Every fourth step from 0, at most four: the steps of the structured noise whose every window's median is 0
+    (test_chain_update_cpu.py counts them per reflected window)."""
+    return np.arange(0, T, 4)[:4]
+
+
+def dense_steps(T):
+    """Six consecutive steps in the middle of the horizon: windows with six non-zero values, a non-zero median."""
+    return np.arange((T - 6) // 2, (T - 6) // 2 + 6)
+
+
+def step_noise(K, T, n, steps, sig, seed):
+    """Host noise (K, T, n) fp32, N(0, diag Sigma) at `steps` and +0 everywhere else."""
+    eps = np.zeros((K, T, n), dtype=np.float32)
+    rng = np.random.default_rng(seed)
+    eps[:, steps] = (rng.normal(size=(K, len(steps), n)) * np.sqrt(np.diag(sig))).astype(np.float32)
+    return eps
+
+
+def clipped_share(un, lo, hi):
+    """The share of the entries of un that lo / hi clip."""
+    return float(np.mean(np.clip(un, lo, hi) != un))
